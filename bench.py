@@ -11,10 +11,16 @@ rather than the 256 MiB Infinity Cache. The fill kernel (the sender's
 materialisation, InitOnceIoPatternCallback's role) builds the arenas untimed.
 Batches are independent, so the headline leg issues step i on engine stream
 i mod S (S = 2): one launch's tail overlaps the next one's ramp-up, as a receiver
-verifying a stream of batches would run. roofline.achieved comes from a separate
-serialized leg (one stream, HIP events), the per-kernel time rocprof reports.
+verifying a stream of batches would run.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the line. --full adds
+everything else: roofline.achieved from a separate serialized leg (one stream, HIP
+events: the per-kernel time rocprof reports; a plain run derives it from the
+headline leg's events), the parity checks against the corruption plan, the CPU
+baselines, the extras and the single-process leg. --dump-outputs DIR writes the
+last timed step's outputs (records, first-failure slots, counters) as DIR/*.npy.
+
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
         N>1: either form works; with no WORLD_SIZE in the environment, `bench.py --gpus N` starts the N ranks
         itself as a child `torch.distributed.run` (before anything touches the GPU) and exits with its code:
           python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
@@ -22,8 +28,8 @@ Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
         A WORLD_SIZE that differs from --gpus is an error (exit 2): the line's n_gpus is what ran.
 Each rank verifies its own shard (no data-path collective: "scaling": "weak");
 one RCCL all-reduce of the 5 ctsStatistics-style counters closes the timed region.
-After it, at every N, rank 0 times the CPU oracle over its own batch (cpu_baseline; the other ranks wait on a
-gloo barrier) and the single-process leg (`--engines N`, one process driving all N GPUs, run as a child
+After it, with --full, at every N, rank 0 times the CPU oracle over its own batch (cpu_baseline; the other ranks wait
+on a gloo barrier) and the single-process leg (`--engines N`, one process driving all N GPUs, run as a child
 process) and puts both into the same line. Rank 0 prints ONE JSON line.
 """
 from __future__ import annotations
@@ -52,12 +58,20 @@ def parse():
     p.add_argument("--steps", type=int, default=20,
                    help="timed steps; a step = one rotation over the R arenas = R config-2 batches (R launches)")
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline leg: the serialized roofline leg, the parity checks against "
+                        "the corruption plan, the CPU baselines, the extras (fill, datagram, shards, loopback, host), "
+                        "the single-process leg and, at N > 1, the all-reduce latency. Without it the run sets up, "
+                        "warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last step's launches left (the per-buffer records by "
+                        "field, the per-connection first-failure slots, the counter block) as DIR/<name>.npy, float64")
     p.add_argument("--arenas", type=int, default=8, help="rotated copies of the batch (defeat the 256 MiB MALL)")
     p.add_argument("--buffers", type=int, default=4096)
     p.add_argument("--cpu-seconds", type=float, default=6.0, help="budget per CPU-baseline leg")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extras", action="store_true", help="skip fill / datagram / host-path extras")
-    p.add_argument("--extras-only", default="", help="comma list: fill,datagram,host,loopback")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    p.add_argument("--no-extras", action="store_true", help="with --full: skip fill / datagram / host-path extras")
+    p.add_argument("--extras-only", default="", help="with --full, comma list: fill,datagram,host,loopback")
     p.add_argument("--stream", choices=["new", "default"], default="default",
                    help="launch stream: a new HIP stream or the device's default stream")
     p.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -89,7 +103,8 @@ def parse():
                         "verifies answer faster there, but whole loopback runs were not faster "
                         "(profiles/r02/numa/); the device-resident legs do not care")
     p.add_argument("--no-engines-leg", action="store_true",
-                   help="skip the single-process leg (--engines N as a child process) in the line's extras")
+                   help="with --full: skip the single-process leg (--engines N as a child process) in the line's "
+                        "extras")
     p.add_argument("--stub-gpu", action="store_true",
                    help="launcher test: every rank reports its RANK/WORLD_SIZE over gloo and rank 0 prints one line; "
                         "nothing touches a GPU (tests/test_bench_launcher.py)")
@@ -102,7 +117,12 @@ def parse():
                    help="with --stub-gpu: this rank fails (tests/test_bench_launcher.py)")
     p.add_argument("--stub-fail-mode", choices=["raise", "stall"], default="raise",
                    help="with --stub-fail-rank: raise before the all-gather, or sleep past --dist-timeout")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.dump_outputs and (args.engines > 0 or args.stub_gpu):
+        p.error("--dump-outputs writes the default leg's outputs (not --engines / --stub-gpu)")
+    return args
 
 
 # environment keys of a torch.distributed.run rank; a child started from a rank (the single-process leg) drops
@@ -304,6 +324,24 @@ class Batch:
             ok &= bool(np.array_equal(self.cff[r].cpu().numpy().view(np.uint32), self.exp_cff))
         return ok
 
+    def dump_outputs(self, path):
+        """--dump-outputs: what cts_verify's caller holds after the last timed step (one launch per arena), as
+        `path`/<name>.npy in float64 (every value is an integer below 2^53, so exact): the records' fields as
+        [R, n] arrays, the first-failure slots as [R, n] (an empty slot, 0xFFFFFFFF, as -1), and the six counters
+        the block accumulated over all timed launches, in COUNTER_FIELDS_EX order. R * n * 7 * 8 bytes: 1.75 MiB at
+        the default 8 x 4096."""
+        from ctstraffic_amd.engine import results_from_device
+        from ctstraffic_amd.types import COUNTER_FIELDS_EX, RESULT_DTYPE
+
+        os.makedirs(path, exist_ok=True)
+        res = [results_from_device(t) for t in self.results]
+        for f in RESULT_DTYPE.names:
+            np.save(os.path.join(path, "records_%s.npy" % f), np.stack([r[f] for r in res]).astype(np.float64))
+        np.save(os.path.join(path, "conn_first_fail.npy"),
+                np.stack([c.cpu().numpy() for c in self.cff]).astype(np.float64))
+        ctr = self.engine.read_counters_ex(self.counters)
+        np.save(os.path.join(path, "counters.npy"), np.array([ctr[f] for f in COUNTER_FIELDS_EX], dtype=np.float64))
+
 
 def main():
     args = parse()
@@ -433,18 +471,19 @@ def main():
             stream.wait_event(ev)
 
     # ---- warmup -------------------------------------------------------------------------------
-    run_steps(max(args.warmup, 1))
+    if args.full:  # the serialized launches of the roofline leg below
+        run_steps(max(args.warmup, 1))
     run_pipelined(max(args.warmup, 1))
     torch.cuda.synchronize()
     K = args.steps
     launches = K * R
 
-    # ---- roofline leg: serialized launches on one stream, HIP events around exactly the K*R launches.
+    # ---- roofline leg (--full): serialized launches on one stream, HIP events around exactly the K*R launches.
     # This is the per-kernel duration rocprof reports (run with --pipeline-streams 1 for the trace).
     avg_kernel_s = None
     ser_ok = True
     serial_graph = False
-    if pipe:
+    if pipe and args.full:
         engine.reset_counters(counters, stream=stream)
         ev_a = torch.cuda.Event(enable_timing=True)
         ev_b = torch.cuda.Event(enable_timing=True)
@@ -536,23 +575,30 @@ def main():
     # reports
     if avg_kernel_s is None:
         avg_kernel_s = pipe_launch_s
-    local_ctr = engine.read_counters(counters)
-    # the DataError count: every arena's slots were emptied before the timed region, so its first launch claims
-    # the batch's failed connections and the later rotations find them claimed (one per connection,
-    # ctsSocketState.cpp:221-228)
-    conns_failed = engine.read_counters_ex(counters)["connections_failed"]
-    exp_conns = int((B.exp_cff != 0xFFFFFFFF).sum()) * R
-    outputs_ok = B.outputs_ok()
-    parity_ok = (ser_ok and outputs_ok and local_ctr == {k: v * launches for k, v in exp_ctr.items()} and
-                 conns_failed == exp_conns)
-    if world > 1:
-        glob = D.counters_dict(ctr_reduced)
-        exp_glob = {f: exp_ctr[f] * launches * world for f in exp_ctr}
-        exp_glob["connections_failed"] = exp_conns * world
-        parity_ok = parity_ok and glob == exp_glob
-        ok_t = torch.tensor([1 if parity_ok else 0], device=dev)
-        dist.all_reduce(ok_t, op=dist.ReduceOp.MIN)
-        parity_ok = bool(ok_t.item())
+    if args.dump_outputs and rank == 0:
+        B.dump_outputs(args.dump_outputs)
+    parity = None
+    if args.full:
+        local_ctr = engine.read_counters(counters)
+        # the DataError count: every arena's slots were emptied before the timed region, so its first launch claims
+        # the batch's failed connections and the later rotations find them claimed (one per connection,
+        # ctsSocketState.cpp:221-228)
+        conns_failed = engine.read_counters_ex(counters)["connections_failed"]
+        exp_conns = int((B.exp_cff != 0xFFFFFFFF).sum()) * R
+        outputs_ok = B.outputs_ok()
+        parity_ok = (ser_ok and outputs_ok and local_ctr == {k: v * launches for k, v in exp_ctr.items()} and
+                     conns_failed == exp_conns)
+        if world > 1:
+            glob = D.counters_dict(ctr_reduced)
+            exp_glob = {f: exp_ctr[f] * launches * world for f in exp_ctr}
+            exp_glob["connections_failed"] = exp_conns * world
+            parity_ok = parity_ok and glob == exp_glob
+            ok_t = torch.tensor([1 if parity_ok else 0], device=dev)
+            dist.all_reduce(ok_t, op=dist.ReduceOp.MIN)
+            parity_ok = bool(ok_t.item())
+        parity = {"counters_match_expected": bool(parity_ok), "records_and_first_fail_match": bool(outputs_ok),
+                  "counters": {**local_ctr, "connections_failed": conns_failed},
+                  "connections_failed_expected": exp_conns}
 
     total_bytes = bytes_per_step * K * world
     value = total_bytes / elapsed / GIB
@@ -560,7 +606,7 @@ def main():
 
     # allreduce latency (separately, outside the headline)
     allreduce_us = None
-    if world > 1:
+    if world > 1 and args.full:
         torch.cuda.synchronize()
         ta = time.perf_counter()
         for _ in range(20):
@@ -570,7 +616,7 @@ def main():
 
     extras = {}
     cpu = None
-    if rank == 0:
+    if rank == 0 and args.full:
         want = set(x for x in args.extras_only.split(",") if x) or {"fill", "datagram", "host", "loopback", "shards"}
         if not args.no_extras and world == 1:
             extras = run_extras(engine, torch, W, w, B.arenas, B.descs, dev, want)
@@ -643,6 +689,9 @@ def main():
                 "per_rank_avg_kernel_us": diag["per_rank_avg_kernel_us"],
                 "timing": ("HIP events on the launch stream around the K*R timed launches (%s), / (K*R)"
                            % ("HIP-graph replays" if graph is not None else "host launches")) if not pipe else
+                          ("HIP events around the headline leg's K*R pipelined launches, / (K*R): the span per launch "
+                           "with one launch's tail under the next one's ramp-up, not a kernel's duration (--full "
+                           "times the serialized leg)") if not args.full else
                           ("separate serialized leg of K*R launches on one stream (%s), HIP events around them, "
                            "/ (K*R) (the per-kernel duration rocprof reports); the headline value is the pipelined leg"
                            % (("%d replay(s) of a HIP graph of %d rotation(s), after an untimed upload replay"
@@ -660,10 +709,9 @@ def main():
                     "wall_minus_events_us": round((elapsed - pipe_launch_s * launches) * 1e6, 1),
                 },
             },
+            "full": bool(args.full),
             "cpu_baseline": cpu,
-            "parity": {"counters_match_expected": bool(parity_ok), "records_and_first_fail_match": bool(outputs_ok),
-                       "counters": {**local_ctr, "connections_failed": conns_failed},
-                       "connections_failed_expected": exp_conns},
+            "parity": parity,
         }
         line["per_rank_GiBps"] = [round(x, 1) for x in per_rank]
         line.update({k: v for k, v in diag.items() if k != "per_rank_avg_kernel_us"})

@@ -78,7 +78,7 @@ def test_engines_leg_native_threads(engines):
 @pytest.mark.parametrize("launcher", ["native", "python"])
 def test_headline_launchers(launcher):
     j = _run("--launcher", launcher, "--steps", "3", "--warmup", "1", "--arenas", "2", "--buffers", "2048",
-             "--no-cpu-baseline", "--no-extras", "--no-engines-leg")
+             "--full", "--no-cpu-baseline", "--no-extras", "--no-engines-leg")  # --full: the parity checks
     assert j["parity"]["counters_match_expected"] and j["parity"]["records_and_first_fail_match"]
     assert j["config"]["launcher"].startswith(launcher)
     assert j["parity"]["counters"]["buffers_checked"] == 2048 * 3 * 2

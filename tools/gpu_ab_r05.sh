@@ -10,7 +10,7 @@ done
 echo "[$(date +%T)] tail"
 timeout -k 10 150 tools/verify_timeline 3 64 tail > $O/tail.jsonl 2>&1
 echo "[$(date +%T)] bench"
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python bench.py --full >$O/bench.json 2> $O/bench.err
 echo "[$(date +%T)] engines"
 timeout -k 10 240 python bench.py --engines 1 --no-cpu-baseline --no-extras > $O/engines1.json 2> $O/engines1.err
 timeout -k 10 240 python bench.py --engines 2 --engines-same-gpu --no-cpu-baseline --no-extras > $O/engines2same.json 2> $O/engines2same.err

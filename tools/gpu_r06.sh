@@ -44,17 +44,17 @@ fi
 if [[ $STEPS == *fillx* ]]; then
   # the fill extras alone (fill_GBps, the fill+verify pairs) through the C ABI
   run bench-fill-extras
-  timeout -k 10 300 python bench.py --no-cpu-baseline --extras-only fill --no-engines-leg --steps 5 --warmup 2 \
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --extras-only fill --no-engines-leg --steps 5 --warmup 2 \
     > "$O/bench_fill.json" 2> "$O/bench_fill.err"
 fi
 if [[ $STEPS == *dgx* ]]; then
   # the datagram extras alone (config-3 verify, MediaStream receive forms and fills)
   run bench-datagram-extras
-  timeout -k 10 300 python bench.py --no-cpu-baseline --extras-only datagram --no-engines-leg --steps 5 --warmup 2 \
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --extras-only datagram --no-engines-leg --steps 5 --warmup 2 \
     > "$O/bench_datagram.json" 2> "$O/bench_datagram.err"
 fi
 if [[ $STEPS == *bench* ]]; then
   run bench
-  timeout -k 10 500 python bench.py > "$O/bench.json" 2> "$O/bench.err"
+  timeout -k 10 500 python bench.py --full >"$O/bench.json" 2> "$O/bench.err"
 fi
 run done

@@ -20,7 +20,7 @@ if [[ $STEPS == all || $STEPS == *tests* ]]; then
 fi
 if [[ $STEPS == all || $STEPS == *bench* ]]; then
   run bench
-  timeout -k 10 400 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 400 python bench.py --full >"$OUT/bench.json" 2> "$OUT/bench.err"
 fi
 if [[ $STEPS == all || $STEPS == *engines* ]]; then
   # single-process multi-GPU leg (the ctsTraffic process model) at the GPUs this box has
@@ -39,7 +39,7 @@ if [[ $STEPS == all || $STEPS == *dist* ]]; then
   # 2-rank rehearsal of the multi-GPU path on this one GPU (gloo; both ranks on cuda:0)
   run dist-rehearsal
   # bench.py --gpus 2 starts its two ranks itself (a child torch.distributed.run), both on this one GPU over gloo
-  timeout -k 10 300 python bench.py --gpus 2 --dist-backend gloo --no-extras --cpu-seconds 2 --steps 50 --warmup 5 \
+  timeout -k 10 300 python bench.py --gpus 2 --dist-backend gloo --full --no-extras --cpu-seconds 2 --steps 50 --warmup 5 \
     > "$OUT/dist2_gloo.json" 2> "$OUT/dist2_gloo.err"
 fi
 if [[ $STEPS == all || $STEPS == *prof* ]]; then
@@ -55,18 +55,18 @@ if [[ $STEPS == all || $STEPS == *prof* ]]; then
   # its pipelined leg as two bursts (tools/prof_summary.py: wall per launch, overlap)
   run rocprof-pipelined-kernel-trace
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -T -d "$OUT/prof_pipe_kt" -o run --output-format csv \
-    -- python3 bench.py --no-cpu-baseline --no-extras --steps 200 --warmup 20 > "$OUT/prof_pipe_kt_bench.json" 2> "$OUT/prof_pipe_kt.err"
+    -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 200 --warmup 20 >"$OUT/prof_pipe_kt_bench.json" 2> "$OUT/prof_pipe_kt.err"
 fi
 if [[ $STEPS == all || $STEPS == *dgprof* ]]; then
   # config 3 (16 M datagrams): the bench's datagram extras under the same two profilers
   run rocprof-datagram-kernel-trace
   # (no -T: the MediaStream kernel's descriptor and strided-ring forms differ only in a template argument)
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_dg_kt" -o run --output-format csv \
-    -- python3 bench.py --no-cpu-baseline --extras-only datagram --steps 5 --warmup 2 > "$OUT/prof_dg_kt_bench.json" 2> "$OUT/prof_dg_kt.err"
+    -- python3 bench.py --full --no-cpu-baseline --extras-only datagram --steps 5 --warmup 2 > "$OUT/prof_dg_kt_bench.json" 2> "$OUT/prof_dg_kt.err"
   for ctr in FETCH_SIZE WRITE_SIZE; do
     run rocprof-datagram-pmc $ctr
     timeout -k 10 300 rocprofv3 --pmc $ctr --kernel-trace -d "$OUT/prof_dg_pmc_$ctr" -o run --output-format csv \
-      -- python3 bench.py --no-cpu-baseline --extras-only datagram --steps 5 --warmup 2 > "$OUT/prof_dg_pmc_$ctr.json" 2> "$OUT/prof_dg_pmc_$ctr.err"
+      -- python3 bench.py --full --no-cpu-baseline --extras-only datagram --steps 5 --warmup 2 > "$OUT/prof_dg_pmc_$ctr.json" 2> "$OUT/prof_dg_pmc_$ctr.err"
   done
 fi
 if [[ $STEPS == *timeline* ]]; then
@@ -92,7 +92,7 @@ if [[ $STEPS == *serial_ab* ]]; then
   for rep in 1 2 3; do
     for g in 0 1; do
       run serial-ab $rep $g
-      timeout -k 10 200 python bench.py --no-extras --no-cpu-baseline --serial-graph-rotations $g \
+      timeout -k 10 200 python bench.py --full --no-extras --no-cpu-baseline --serial-graph-rotations $g \
         >> "$OUT/serial_ab.jsonl" 2>> "$OUT/serial_ab.err"
     done
   done

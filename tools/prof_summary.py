@@ -101,7 +101,7 @@ def _by_kernel(rows, value):
 
 
 def _pipelined(tr):
-    """Bursts of config-2 verify launches (gaps > 200 us split them) in a default bench.py run: the
+    """Bursts of config-2 verify launches (gaps > 200 us split them) in a `bench.py --full` run: the
     serialized roofline leg and the pipelined headline leg. Per burst: launches, grids, wall span /
     launch (first start to last end), mean kernel duration, and how many launches start before the
     previous one ends (overlap)."""
