@@ -1,5 +1,5 @@
 // cts_media_stream_client.hpp — the MediaStream client's frame accounting (cts_media_stream.cpp) as the
-// MediaStream client pattern of the ctsIoPattern mirror (cts_pattern.cpp) drives it: one datagram and one
+// MediaStream client pattern of the ctsIoPattern mirror (MediaStreamClient, cts_pattern_media_stream.cpp) drives it: one datagram and one
 // renderer-timer tick at a time, with the pattern (not the accounting object) owning the connection's status.
 // Host-only (no HIP types): the sanitizer builds compile it with g++.
 #pragma once

@@ -1,5 +1,5 @@
 // engine_stub.cpp — link-time fakes for the device half of libcts_engine.so, so the host C++
-// (cts_pattern.cpp, cts_media_stream.cpp, cts_status.cpp, cts_loopback.cpp) can be built with
+// (cts_pattern*.cpp, cts_media_stream.cpp, cts_status.cpp, cts_loopback.cpp) can be built with
 // g++ under AddressSanitizer/UBSan/ThreadSanitizer on a machine without a GPU. This is how the
 // reference's own MSTest projects replace ctsConfig (link-time fakes, no mocks).
 // Every device entry point fails with CTS_E_NO_DEVICE; host allocations come from malloc.

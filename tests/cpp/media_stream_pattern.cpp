@@ -1,4 +1,4 @@
-// media_stream_pattern.cpp — the MediaStream patterns of the ctsIoPattern mirror (cts_pattern.cpp) under the
+// media_stream_pattern.cpp — the MediaStream patterns of the ctsIoPattern mirror (cts_pattern_media_stream.cpp) under the
 // sanitizers. Each run pairs a server pattern with a client pattern, as ctsMediaStreamServer and ctsMediaStreamClient
 // drive them: the server's connection-id datagram and frame tasks become the client's datagrams (split by
 // cts_media_stream_split, header + sender-buffer payload, a few dropped or repeated), delivered by a receive thread

@@ -1,6 +1,6 @@
 """Host C++ under sanitizers (the reference has none; "ASan/UBSan on host code").
 
-The host half of the engine — the ctsIoPattern mirror (cts_pattern.cpp), MediaStream framing and
+The host half of the engine — the ctsIoPattern mirror (cts_pattern*.cpp), MediaStream framing and
 client accounting (cts_media_stream.cpp), status output (cts_status.cpp) and the loopback feeder
 with its sync and async functors (cts_loopback.cpp) — is built from source with g++ against
 link-time fakes of the device entry points (tests/cpp/engine_stub.cpp), with the oracle's C
@@ -19,7 +19,8 @@ import tempfile
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST_SRCS = ["cts_pattern.cpp", "cts_media_stream.cpp", "cts_status.cpp", "cts_loopback.cpp", "cts_loopback_udp.cpp",
+HOST_SRCS = ["cts_pattern.cpp", "cts_pattern_state.cpp", "cts_pattern_pipeline.cpp", "cts_pattern_media_stream.cpp",
+             "cts_pattern_process.cpp", "cts_media_stream.cpp", "cts_status.cpp", "cts_loopback.cpp", "cts_loopback_udp.cpp",
              "cts_host_util.cpp", "cts_collective.cpp"]
 SAN = {
     "plain": [],
@@ -95,7 +96,8 @@ def test_engine_abi_on_eight_fake_devices(san):
     inc = ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "ctstraffic_amd", "csrc"),
            "-I", os.path.join(ROOT, "oracle"), "-I", "/opt/rocm/include", "-D__HIP_PLATFORM_AMD__"]
     srcs = [os.path.join(ROOT, "ctstraffic_amd", "csrc", x) for x in (
-        "cts_engine.cpp", "cts_host_util.cpp", "cts_pattern.cpp", "cts_media_stream.cpp", "cts_status.cpp",
+        "cts_engine.cpp", "cts_host_util.cpp", "cts_pattern.cpp", "cts_pattern_state.cpp", "cts_pattern_pipeline.cpp",
+        "cts_pattern_media_stream.cpp", "cts_pattern_process.cpp", "cts_media_stream.cpp", "cts_status.cpp",
         "cts_loopback.cpp", "cts_loopback_udp.cpp", "cts_collective.cpp")] + [
         os.path.join(ROOT, "tests", "cpp", "engine_devices.cpp"), os.path.join(ROOT, "tools", "bench_multi.cpp")]
     with tempfile.TemporaryDirectory() as d:

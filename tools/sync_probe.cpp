@@ -1,6 +1,6 @@
 // sync_probe.cpp — latency of one SYNC-mode verify (ctsIOPattern.cpp:745-775 called per CompleteIo):
 // a 64 KiB buffer in pinned, device-mapped host memory verified in place over PCIe and waited for,
-// exactly as cts_pattern.cpp VerifyNow does (cts_verify on the pattern's own stream + synchronize).
+// exactly as cts_io_pattern::VerifyNow (cts_pattern.cpp) does (cts_verify on the pattern's own stream + synchronize).
 // Variants: the buffer described as S slices (S descriptors of 64 KiB / S, expected offsets advanced,
 // so S workgroups/waves issue their PCIe reads at once) and T threads, each with its own stream,
 // buffer, descriptor and result (T connections completing concurrently). Wait = hipStreamSynchronize
