@@ -87,6 +87,22 @@ class CtsCountersEx(ctypes.Structure):
         return {f: int(getattr(self, f)) for f, _ in self._fields_}
 
 
+class CtsCountersRef(ctypes.Structure):
+    """cts_counters_ref: the reference view of a counter block, every connection stopped at its first failing
+    buffer (laid out like cts_counters_ex: six u64)."""
+    _fields_ = [
+        ("bytes_recv", ctypes.c_uint64),
+        ("bytes_ok", ctypes.c_uint64),
+        ("buffers_recv", ctypes.c_uint64),
+        ("buffers_failed", ctypes.c_uint64),
+        ("bytes_after_failure", ctypes.c_uint64),
+        ("buffers_after_failure", ctypes.c_uint64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
 class CtsAllreduceSetup(ctypes.Structure):
     """cts_allreduce_setup: where the newest RCCL clique's set-up time went (ms)."""
     _fields_ = [
@@ -146,6 +162,15 @@ def _declare(L: ctypes.CDLL) -> None:
         "cts_fill": ([P, P, u64, P, u32, u32, P], i32),
         "cts_verify": ([P, P, u64, P, u32, u32, P, P, P, u32, P], i32),
         "cts_verify_strided": ([P, P, u64, u32, P, u32, u32, u32, u32, P, P, P, u32, P], i32),
+        "cts_verify_at": ([P, P, u64, P, u32, u32, u32, P, P, P, u32, P], i32),
+        "cts_verify_strided_at": ([P, P, u64, u32, P, u32, u32, u32, u32, u32, P, P, P, u32, P], i32),
+        "cts_refview_accumulate": ([P, u64, P, u32, u32, P, u32, P, P], i32),
+        "cts_refview_accumulate_strided": ([P, u64, u32, P, u32, u32, u32, u32, P, u32, P, P], i32),
+        "cts_counters_read_ref": ([P, P, ctypes.POINTER(CtsCountersRef), P], i32),
+        "cts_counters_read_multi_ref": ([ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), u32,
+                                         ctypes.POINTER(CtsCountersRef)], i32),
+        "cts_counters_allreduce_ref": ([ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), u32,
+                                        ctypes.POINTER(CtsCountersRef)], i32),
         "cts_counters_device_bytes": ([], ctypes.c_size_t),
         "cts_counters_reset": ([P, P, P], i32),
         "cts_counters_read": ([P, P, ctypes.POINTER(CtsCounters), P], i32),

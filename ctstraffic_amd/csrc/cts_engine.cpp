@@ -531,6 +531,12 @@ Mailbox::~Mailbox()
     if (slots) (void)hipHostFree(slots);
 }
 
+const cts::LaunchGeometry& cts::engine_geometry(const cts_engine* e, int* device)
+{
+    if (device != nullptr) *device = e->device;
+    return e->geo;
+}
+
 extern "C" {
 
 const char* cts_version(void) { return "ctstraffic_amd 0.3.0 (gfx950)"; }

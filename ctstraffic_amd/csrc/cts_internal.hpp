@@ -137,6 +137,31 @@ hipError_t launch_verify_strided(const uint8_t* arena, uint64_t arena_bytes, uin
                                  cts_verify_result* results, uint64_t* counters, uint32_t* conn_first_fail,
                                  uint32_t n_conns, hipStream_t stream, const LaunchGeometry& geo);
 
+// The same two launches with the stream ordinal of buffer 0 (cts_verify_at / cts_verify_strided_at): the DataError
+// slots take base_index + i. launch_verify and launch_verify_strided forward here with base 0.
+hipError_t launch_verify_at(const uint8_t* arena, uint64_t arena_bytes, const cts_buf_desc* descs, uint32_t n,
+                            uint32_t max_length_hint, cts_verify_result* results, uint64_t* counters,
+                            uint32_t* conn_first_fail, uint32_t n_conns, uint32_t base_index, hipStream_t stream,
+                            const LaunchGeometry& geo);
+hipError_t launch_verify_strided_at(const uint8_t* arena, uint64_t arena_bytes, uint32_t stride, const uint32_t* lens,
+                                    uint32_t n, uint32_t skip_head, uint32_t expected, uint32_t conn_index,
+                                    cts_verify_result* results, uint64_t* counters, uint32_t* conn_first_fail,
+                                    uint32_t n_conns, uint32_t base_index, hipStream_t stream,
+                                    const LaunchGeometry& geo);
+
+// The reference-view pass over a batch's descriptors (cts_refview_accumulate / _strided); reads no arena byte.
+hipError_t launch_refview(uint64_t arena_bytes, const cts_buf_desc* descs, uint32_t n, uint32_t base_index,
+                          const uint32_t* conn_first_fail, uint32_t n_conns, uint64_t* ref_counters, hipStream_t stream,
+                          const LaunchGeometry& geo);
+hipError_t launch_refview_strided(uint64_t arena_bytes, uint32_t stride, const uint32_t* lens, uint32_t n,
+                                  uint32_t skip_head, uint32_t conn_index, uint32_t base_index,
+                                  const uint32_t* conn_first_fail, uint32_t n_conns, uint64_t* ref_counters,
+                                  hipStream_t stream, const LaunchGeometry& geo);
+
+// The engine's device and launch geometry for the entry points that live outside cts_engine.cpp (cts_refview.cpp);
+// e != nullptr. Defined in cts_engine.cpp, where cts_engine is complete.
+const LaunchGeometry& engine_geometry(const cts_engine* e, int* device);
+
 hipError_t launch_fill(uint8_t* arena, uint64_t arena_bytes, const cts_buf_desc* descs, uint32_t n,
                        uint32_t max_length_hint, hipStream_t stream, const LaunchGeometry& geo);
 

@@ -19,8 +19,10 @@
 // compute the first differing byte and the differing-byte count.
 //
 // Paths (one kernel per path; nontemporal and plain-load forms of each):
-//   verify_wg_kernel                  one 256-lane workgroup per buffer (64 KiB TCP buffers)
+//   verify_wg_kernel                  one 256-lane workgroup per buffer (64 KiB TCP buffers); verify_wg_ordinal is the
+//                                     same body with cts_verify_at's base_index argument
 //   verify_quad_kernel                four buffers per wave (datagram-sized buffers; descriptors or a strided ring)
+//   refview_accumulate                the reference view of a verified batch: descriptors and DataError slots only
 //   media_stream_verify_quad_kernel   MediaStream receive: header + payload, four datagrams per wave
 //   fill_kernel / fill_span_kernel / fill_batched_kernel / media_stream_fill_ring_kernel   the sender side
 //   mailbox_kernel                    SYNC-mode VerifyBuffer without a launch per call (resident grid)
@@ -526,10 +528,12 @@ __device__ __forceinline__ void write_bad(cts_verify_result* results, uint32_t i
 
 // Record one verified buffer (called by the team leader).
 // rslot != nullptr: the record goes there (an LDS staging slot) instead of to results[i].
+// base_index: the stream ordinal of the launch's buffer 0 (cts_verify_at); only the DataError slot takes
+// base_index + i, the record stays at the launch-local i.
 __device__ __forceinline__ void finish_buffer(const Span& s, const cts_buf_desc& d, uint32_t i, uint32_t first,
                                               uint32_t count, cts_verify_result* results, uint64_t* tc,
                                               uint32_t* conn_first_fail, uint32_t n_conns,
-                                              cts_verify_result* rslot = nullptr)
+                                              cts_verify_result* rslot = nullptr, uint32_t base_index = 0u)
 {
     const bool pass = (first == kNone);
     if (rslot != nullptr) {
@@ -560,7 +564,7 @@ __device__ __forceinline__ void finish_buffer(const Span& s, const cts_buf_desc&
         tc[kBuffersFailed] += 1;
         tc[kMismatchedBytes] += count;
         if (conn_first_fail != nullptr && d.conn_index < n_conns &&
-            atomicMin(&conn_first_fail[d.conn_index], i) == 0xFFFFFFFFu)
+            atomicMin(&conn_first_fail[d.conn_index], base_index + i) == 0xFFFFFFFFu)
             tc[kConnectionsFailed] += 1;
     }
 }
@@ -631,10 +635,11 @@ __device__ __forceinline__ void block_reduce_mismatch(uint32_t& first, uint32_t&
 constexpr int kWgLoads = 2;  // loads per lane per round: 4 workgroups x 4 waves x 2 = 32 KiB in flight per CU
 
 template <bool NT>
-__global__ void __launch_bounds__(kBlock, 4)
-    verify_wg_kernel(const uint8_t* __restrict__ arena, uint64_t arena_bytes, const cts_buf_desc* __restrict__ descs,
-                     uint32_t n, cts_verify_result* __restrict__ results, uint64_t* __restrict__ counters,
-                     uint32_t* __restrict__ conn_first_fail, uint32_t n_conns)
+__device__ __forceinline__ void verify_wg_body(const uint8_t* __restrict__ arena, uint64_t arena_bytes,
+                                               const cts_buf_desc* __restrict__ descs, uint32_t n,
+                                               cts_verify_result* __restrict__ results, uint64_t* __restrict__ counters,
+                                               uint32_t* __restrict__ conn_first_fail, uint32_t n_conns,
+                                               uint32_t base_index)
 {
     __shared__ uint64_t ctr[1][kCounterCount];
     const uint32_t lane = threadIdx.x;
@@ -670,9 +675,32 @@ __global__ void __launch_bounds__(kBlock, 4)
                 block_reduce_mismatch(first, count);
             }
         }
-        if (lane == 0) finish_buffer(s, d, i, first, count, results, ctr[0], conn_first_fail, n_conns);
+        if (lane == 0)
+            finish_buffer(s, d, i, first, count, results, ctr[0], conn_first_fail, n_conns, nullptr, base_index);
     }
     flush_counters<1>(counters, ctr);
+}
+
+// cts_verify: the DataError slots take launch-local indices. Its name and its eight arguments are what the
+// profiling tools and tests/test_abi.py look the headline kernel up by, so they stay as they are.
+template <bool NT>
+__global__ void __launch_bounds__(kBlock, 4)
+    verify_wg_kernel(const uint8_t* __restrict__ arena, uint64_t arena_bytes, const cts_buf_desc* __restrict__ descs,
+                     uint32_t n, cts_verify_result* __restrict__ results, uint64_t* __restrict__ counters,
+                     uint32_t* __restrict__ conn_first_fail, uint32_t n_conns)
+{
+    verify_wg_body<NT>(arena, arena_bytes, descs, n, results, counters, conn_first_fail, n_conns, 0u);
+}
+
+// cts_verify_at with a nonzero base: the same body, the slots take base_index + i (stream ordinals). 15 argument
+// dwords, still inside the 16 preloaded SGPRs; base_index is read on the failing branch only.
+template <bool NT>
+__global__ void __launch_bounds__(kBlock, 4)
+    verify_wg_ordinal(const uint8_t* __restrict__ arena, uint64_t arena_bytes, const cts_buf_desc* __restrict__ descs,
+                      uint32_t n, cts_verify_result* __restrict__ results, uint64_t* __restrict__ counters,
+                      uint32_t* __restrict__ conn_first_fail, uint32_t n_conns, uint32_t base_index)
+{
+    verify_wg_body<NT>(arena, arena_bytes, descs, n, results, counters, conn_first_fail, n_conns, base_index);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1001,7 +1029,7 @@ template <bool NT, bool STRIDED>
 __global__ void __launch_bounds__(kBlock)
     verify_quad_kernel(const uint8_t* __restrict__ arena, uint64_t arena_bytes, VSource src, uint32_t n,
                        cts_verify_result* __restrict__ results, uint64_t* __restrict__ counters,
-                       uint32_t* __restrict__ conn_first_fail, uint32_t n_conns, uint32_t per)
+                       uint32_t* __restrict__ conn_first_fail, uint32_t n_conns, uint32_t per, uint32_t base_index)
 {
     constexpr int TEAMS = kBlock / kQuadTeam;
     __shared__ uint64_t ctr[TEAMS][kCounterCount];
@@ -1047,7 +1075,7 @@ __global__ void __launch_bounds__(kBlock)
                                                         q.sp[first], 0u, 0u));
                 qc.add(q.len, pass, count);
                 if (!pass && conn_first_fail != nullptr && d.conn_index < n_conns &&
-                    atomicMin(&conn_first_fail[d.conn_index], i) == 0xFFFFFFFFu)
+                    atomicMin(&conn_first_fail[d.conn_index], base_index + i) == 0xFFFFFFFFu)
                     qc.conns += 1u;  // this connection's first recorded failure (kConnectionsFailed)
             }
         }
@@ -1055,6 +1083,101 @@ __global__ void __launch_bounds__(kBlock)
         w.i = inext;
     }
     qc.flush<TEAMS>(ctr, team, lane, counters);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The reference view of a verified batch (cts_refview_accumulate): what ctsTraffic would have counted, which
+// fails a connection on its first failing VerifyBuffer (ctsIOPattern.cpp:486-489 -> FailedIo) and receives
+// nothing of it afterwards. Descriptors only, the arena is never read: buffer i has the stream ordinal
+// g = base_index + i, its connection's DataError slot F holds the first failing ordinal (cts_verify_at), and
+// the buffer counts as received when g <= F, as clean when g < F, as the failing one when g == F and as
+// never received when g > F. Bad descriptors (the verify's desc_bad) count nowhere, as in the verify.
+// One descriptor per lane per step, grid-stride: a wave's loads cover 64 x 24 contiguous bytes (or 64 x 4 of a
+// strided ring's lengths), read once (nontemporal with CTS_ATTR_NT_LOADS); the slot reads are plain gathers
+// that stay in L2 (connection-major batches make them near-broadcasts). The six per-lane sums are reduced by
+// wave shuffles, then over the four waves in LDS, then added to the workgroup's counter shard, the route of
+// flush_counters.
+enum RefSlot {
+    kRefBytesRecv = 0,
+    kRefBytesOk = 1,
+    kRefBuffersRecv = 2,
+    kRefBuffersFailed = 3,
+    kRefBytesAfterFailure = 4,
+    kRefBuffersAfterFailure = 5
+};
+static_assert(kRefBuffersAfterFailure + 1 == kCounterCount, "a reference-view block folds like a counter block");
+
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, off, 64);
+    return v;
+}
+
+template <bool NT, bool STRIDED>
+__device__ __forceinline__ cts_buf_desc refview_desc(const VSource& src, uint64_t i)
+{
+    if constexpr (STRIDED) {
+        const uint32_t len = NT ? __builtin_nontemporal_load(src.lens + i) : src.lens[i];
+        // vs_desc's rule: a completion longer than its slot is a bad descriptor
+        return cts_buf_desc{i * src.stride, len, len <= src.stride ? src.expected : 65536u, src.conn_index,
+                            src.skip_head};
+    } else {
+        // 24 bytes, 8-byte aligned: three 8-byte loads
+        const uint64_t* p = reinterpret_cast<const uint64_t*>(src.descs + i);
+        const uint64_t a = NT ? __builtin_nontemporal_load(p) : p[0];
+        const uint64_t b = NT ? __builtin_nontemporal_load(p + 1) : p[1];
+        const uint64_t c = NT ? __builtin_nontemporal_load(p + 2) : p[2];
+        return cts_buf_desc{a, (uint32_t)b, (uint32_t)(b >> 32), (uint32_t)c, (uint32_t)(c >> 32)};
+    }
+}
+
+template <bool NT, bool STRIDED>
+__global__ void __launch_bounds__(kBlock)
+    refview_accumulate(uint64_t arena_bytes, VSource src, uint32_t n, uint32_t base_index,
+                       const uint32_t* __restrict__ conn_first_fail, uint32_t n_conns, uint64_t* __restrict__ ref)
+{
+    __shared__ uint64_t red[kBlock / 64][kCounterCount];
+    uint64_t bytes_recv = 0, bytes_ok = 0, bytes_after = 0;
+    uint32_t bufs_recv = 0, bufs_failed = 0, bufs_after = 0;  // per lane: fewer than 2^32 buffers per launch
+    const uint64_t step = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += step) {
+        const cts_buf_desc d = refview_desc<NT, STRIDED>(src, i);
+        if (desc_bad(d, arena_bytes)) continue;
+        // a connection without a slot never fails
+        const uint32_t first = d.conn_index < n_conns ? conn_first_fail[d.conn_index] : kNone;
+        const uint32_t g = base_index + (uint32_t)i;  // base_index + n <= 0xFFFFFFFF (checked by the entry point)
+        const uint32_t vlen = d.length - d.skip_head;
+        if (g <= first) {
+            bytes_recv += vlen;
+            bufs_recv += 1u;
+            if (g < first) bytes_ok += vlen;
+            else bufs_failed += 1u;
+        } else {
+            bytes_after += vlen;
+            bufs_after += 1u;
+        }
+    }
+    uint64_t v[kCounterCount];
+    v[kRefBytesRecv] = wave_sum64(bytes_recv);
+    v[kRefBytesOk] = wave_sum64(bytes_ok);
+    v[kRefBuffersRecv] = wave_sum(bufs_recv);  // a wave's 64 lanes of one launch: still below 2^32
+    v[kRefBuffersFailed] = wave_sum(bufs_failed);
+    v[kRefBytesAfterFailure] = wave_sum64(bytes_after);
+    v[kRefBuffersAfterFailure] = wave_sum(bufs_after);
+    if ((threadIdx.x & 63u) == 0u) {
+#pragma unroll
+        for (int k = 0; k < kCounterCount; ++k) red[threadIdx.x / 64][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < (unsigned)kCounterCount) {
+        uint64_t sum = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) sum += red[w][threadIdx.x];
+        if (sum)
+            atomicAdd((unsigned long long*)&ref[(blockIdx.x % CTS_COUNTER_SHARDS) * kCounterSlots + threadIdx.x],
+                      (unsigned long long)sum);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1855,16 +1978,19 @@ static inline ContigGrid contig_grid(uint32_t n, const LaunchGeometry& geo)
 template <bool NT>
 static void launch_verify_nt(const uint8_t* arena, uint64_t arena_bytes, const cts_buf_desc* descs, uint32_t n,
                              bool small, cts_verify_result* results, uint64_t* counters, uint32_t* conn_first_fail,
-                             uint32_t n_conns, hipStream_t stream, const LaunchGeometry& geo)
+                             uint32_t n_conns, uint32_t base_index, hipStream_t stream, const LaunchGeometry& geo)
 {
     if (small) {
         const ContigGrid cg = contig_grid(n, geo);
         verify_quad_kernel<NT, false><<<cg.grid, kBlock, 0, stream>>>(
             arena, arena_bytes, VSource{descs, nullptr, 0u, 0u, 0u, 0u}, n, results, counters, conn_first_fail, n_conns,
-            cg.per);
-    } else {
+            cg.per, base_index);
+    } else if (base_index == 0u) {
         verify_wg_kernel<NT><<<grid_for(n, 1, geo), kBlock, 0, stream>>>(arena, arena_bytes, descs, n, results,
                                                                          counters, conn_first_fail, n_conns);
+    } else {
+        verify_wg_ordinal<NT><<<grid_for(n, 1, geo), kBlock, 0, stream>>>(arena, arena_bytes, descs, n, results,
+                                                                          counters, conn_first_fail, n_conns, base_index);
     }
 }
 
@@ -2108,39 +2234,96 @@ hipError_t launch_counters_fold(const void* block, uint64_t* out, bool accumulat
     return hipGetLastError();
 }
 
-hipError_t launch_verify(const uint8_t* arena, uint64_t arena_bytes, const cts_buf_desc* descs, uint32_t n,
-                         uint32_t max_length_hint, cts_verify_result* results, uint64_t* counters,
-                         uint32_t* conn_first_fail, uint32_t n_conns, hipStream_t stream,
-                         const LaunchGeometry& geo)
+hipError_t launch_verify_at(const uint8_t* arena, uint64_t arena_bytes, const cts_buf_desc* descs, uint32_t n,
+                            uint32_t max_length_hint, cts_verify_result* results, uint64_t* counters,
+                            uint32_t* conn_first_fail, uint32_t n_conns, uint32_t base_index, hipStream_t stream,
+                            const LaunchGeometry& geo)
 {
     if (n == 0) return hipSuccess;
     const bool small = max_length_hint != 0 && max_length_hint <= (uint32_t)geo.small_threshold;
     if (geo.nontemporal) {
         launch_verify_nt<true>(arena, arena_bytes, descs, n, small, results, counters, conn_first_fail, n_conns,
-                               stream, geo);
+                               base_index, stream, geo);
     } else {
         launch_verify_nt<false>(arena, arena_bytes, descs, n, small, results, counters, conn_first_fail, n_conns,
-                                stream, geo);
+                                base_index, stream, geo);
     }
     return hipGetLastError();
 }
 
+hipError_t launch_verify(const uint8_t* arena, uint64_t arena_bytes, const cts_buf_desc* descs, uint32_t n,
+                         uint32_t max_length_hint, cts_verify_result* results, uint64_t* counters,
+                         uint32_t* conn_first_fail, uint32_t n_conns, hipStream_t stream,
+                         const LaunchGeometry& geo)
+{
+    return launch_verify_at(arena, arena_bytes, descs, n, max_length_hint, results, counters, conn_first_fail, n_conns,
+                            0u, stream, geo);
+}
+
 // cts_verify_strided: the small-buffer walk (verify_quad_kernel) over a uniformly strided ring
-hipError_t launch_verify_strided(const uint8_t* arena, uint64_t arena_bytes, uint32_t stride, const uint32_t* lens,
-                                 uint32_t n, uint32_t skip_head, uint32_t expected, uint32_t conn_index,
-                                 cts_verify_result* results, uint64_t* counters, uint32_t* conn_first_fail,
-                                 uint32_t n_conns, hipStream_t stream, const LaunchGeometry& geo)
+hipError_t launch_verify_strided_at(const uint8_t* arena, uint64_t arena_bytes, uint32_t stride, const uint32_t* lens,
+                                    uint32_t n, uint32_t skip_head, uint32_t expected, uint32_t conn_index,
+                                    cts_verify_result* results, uint64_t* counters, uint32_t* conn_first_fail,
+                                    uint32_t n_conns, uint32_t base_index, hipStream_t stream,
+                                    const LaunchGeometry& geo)
 {
     if (n == 0) return hipSuccess;
     const VSource src{nullptr, lens, stride, skip_head, expected, conn_index};
     const ContigGrid cg = contig_grid(n, geo);
     if (geo.nontemporal)
         verify_quad_kernel<true, true><<<cg.grid, kBlock, 0, stream>>>(arena, arena_bytes, src, n, results, counters,
-                                                                       conn_first_fail, n_conns, cg.per);
+                                                                       conn_first_fail, n_conns, cg.per, base_index);
     else
         verify_quad_kernel<false, true><<<cg.grid, kBlock, 0, stream>>>(arena, arena_bytes, src, n, results, counters,
-                                                                        conn_first_fail, n_conns, cg.per);
+                                                                        conn_first_fail, n_conns, cg.per, base_index);
     return hipGetLastError();
+}
+
+hipError_t launch_verify_strided(const uint8_t* arena, uint64_t arena_bytes, uint32_t stride, const uint32_t* lens,
+                                 uint32_t n, uint32_t skip_head, uint32_t expected, uint32_t conn_index,
+                                 cts_verify_result* results, uint64_t* counters, uint32_t* conn_first_fail,
+                                 uint32_t n_conns, hipStream_t stream, const LaunchGeometry& geo)
+{
+    return launch_verify_strided_at(arena, arena_bytes, stride, lens, n, skip_head, expected, conn_index, results,
+                                    counters, conn_first_fail, n_conns, 0u, stream, geo);
+}
+
+// cts_refview_accumulate(_strided): one descriptor per lane, at most kRefviewBlocksPerCu workgroups per CU
+constexpr int kRefviewBlocksPerCu = 8;  // 2048 lanes per CU: every wave slot of the CU holds one
+template <bool STRIDED>
+static hipError_t launch_refview_src(uint64_t arena_bytes, const VSource& src, uint32_t n, uint32_t base_index,
+                                     const uint32_t* conn_first_fail, uint32_t n_conns, uint64_t* ref_counters,
+                                     hipStream_t stream, const LaunchGeometry& geo)
+{
+    if (n == 0) return hipSuccess;
+    const uint64_t want = ((uint64_t)n + kBlock - 1) / kBlock;
+    const uint64_t cap = (uint64_t)(geo.num_cus > 0 ? geo.num_cus : 1) * kRefviewBlocksPerCu;
+    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    if (geo.nontemporal)
+        refview_accumulate<true, STRIDED><<<grid, kBlock, 0, stream>>>(arena_bytes, src, n, base_index, conn_first_fail,
+                                                                       n_conns, ref_counters);
+    else
+        refview_accumulate<false, STRIDED><<<grid, kBlock, 0, stream>>>(arena_bytes, src, n, base_index, conn_first_fail,
+                                                                        n_conns, ref_counters);
+    return hipGetLastError();
+}
+
+hipError_t launch_refview(uint64_t arena_bytes, const cts_buf_desc* descs, uint32_t n, uint32_t base_index,
+                          const uint32_t* conn_first_fail, uint32_t n_conns, uint64_t* ref_counters, hipStream_t stream,
+                          const LaunchGeometry& geo)
+{
+    return launch_refview_src<false>(arena_bytes, VSource{descs, nullptr, 0u, 0u, 0u, 0u}, n, base_index,
+                                     conn_first_fail, n_conns, ref_counters, stream, geo);
+}
+
+hipError_t launch_refview_strided(uint64_t arena_bytes, uint32_t stride, const uint32_t* lens, uint32_t n,
+                                  uint32_t skip_head, uint32_t conn_index, uint32_t base_index,
+                                  const uint32_t* conn_first_fail, uint32_t n_conns, uint64_t* ref_counters,
+                                  hipStream_t stream, const LaunchGeometry& geo)
+{
+    // expected offset 0: the pass reads no pattern, the field only carries vs_desc's length > stride rule
+    return launch_refview_src<true>(arena_bytes, VSource{nullptr, lens, stride, skip_head, 0u, conn_index}, n,
+                                    base_index, conn_first_fail, n_conns, ref_counters, stream, geo);
 }
 
 // grid of the batched datagram fills: whole batches per workgroup, at most ring_fill_blocks_per_cu per CU

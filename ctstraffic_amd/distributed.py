@@ -17,6 +17,10 @@ from typing import Optional
 from .types import COUNTER_FIELDS, COUNTER_FIELDS_EX
 
 COUNTER_SLOTS = 8  # u64 per 64-byte counter shard (cts_internal.hpp kCounterSlots)
+# the six words of a reference-view block (cts_counters_ref, accumulated by Engine.refview): every connection
+# stopped at its first failing buffer, as ctsTraffic counts (ctsIOPattern.cpp:486-489)
+REF_FIELDS = ("bytes_recv", "bytes_ok", "buffers_recv", "buffers_failed", "bytes_after_failure",
+              "buffers_after_failure")
 
 
 def dist_env():
@@ -62,8 +66,8 @@ def new_cpu_group(timeout_s: Optional[float] = DEFAULT_TIMEOUT_S):
 def fold_counters(counter_block, fields=COUNTER_FIELDS):
     """Device counter block (CTS_COUNTER_SHARDS x 8 int64, cts_counters_device_bytes) -> int64[len(fields)], on the
     block's own device (no host round trip). fields=COUNTER_FIELDS_EX adds the DataError count (connections_failed,
-    counted by the verifies given a conn_first_fail array)."""
-    assert tuple(fields) == COUNTER_FIELDS_EX[: len(fields)], fields
+    counted by the verifies given a conn_first_fail array); fields=REF_FIELDS folds a reference-view block."""
+    assert tuple(fields) in (COUNTER_FIELDS_EX[: len(fields)], REF_FIELDS), fields
     return counter_block.view(-1, COUNTER_SLOTS)[:, : len(fields)].sum(0)
 
 
@@ -76,10 +80,11 @@ def allreduce_counters(counters, group=None):
     return counters
 
 
-def counters_dict(counters) -> dict:
-    """Folded counters (5, or 6 with connections_failed) -> {field: value}."""
+def counters_dict(counters, fields=COUNTER_FIELDS_EX) -> dict:
+    """Folded counters (5, or 6 with connections_failed) -> {field: value}; fields=REF_FIELDS names the six words of
+    a folded reference-view block."""
     vals = [int(x) for x in counters.tolist()]
-    return dict(zip(COUNTER_FIELDS_EX, vals))
+    return dict(zip(fields, vals))
 
 
 def max_over_ranks(value: float, device=None, group=None) -> float:
@@ -120,5 +125,5 @@ def gather_rank_rows(row, group=None) -> list:
     return [r.tolist() for r in rows]
 
 
-__all__ = ["dist_env", "init", "new_cpu_group", "DEFAULT_TIMEOUT_S", "fold_counters", "allreduce_counters", "counters_dict", "max_over_ranks",
+__all__ = ["dist_env", "init", "new_cpu_group", "DEFAULT_TIMEOUT_S", "REF_FIELDS", "fold_counters", "allreduce_counters", "counters_dict", "max_over_ranks",
            "data_error_count", "gather_rank_rows"]

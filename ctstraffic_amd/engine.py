@@ -12,7 +12,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import CtsAllreduceSetup, CtsCounters, CtsCountersEx, CtsVerifyResult, check, lib
+from ._lib import CtsAllreduceSetup, CtsCounters, CtsCountersEx, CtsCountersRef, CtsVerifyResult, check, lib
 from .types import DESC_DTYPE, RESULT_DTYPE
 
 try:
@@ -121,6 +121,22 @@ def counters_allreduce_ex(engines: Sequence["Engine"], blocks, streams=None) -> 
     E, C, S, n = _multi_args(engines, blocks, streams)
     out = CtsCountersEx()
     check("cts_counters_allreduce_ex", lib().cts_counters_allreduce_ex(E, C, S, n, ctypes.byref(out)))
+    return out.as_dict()
+
+
+def counters_read_multi_ref(engines: Sequence["Engine"], blocks, streams=None) -> dict:
+    """cts_counters_read_multi_ref: the node-wide reference view (Engine.refview blocks), folded on the host."""
+    E, C, S, n = _multi_args(engines, blocks, streams)
+    out = CtsCountersRef()
+    check("cts_counters_read_multi_ref", lib().cts_counters_read_multi_ref(E, C, S, n, ctypes.byref(out)))
+    return out.as_dict()
+
+
+def counters_allreduce_ref(engines: Sequence["Engine"], blocks, streams=None) -> dict:
+    """cts_counters_allreduce_ref: the node-wide reference view reduced on the GPUs (the same u64 x 6 over RCCL)."""
+    E, C, S, n = _multi_args(engines, blocks, streams)
+    out = CtsCountersRef()
+    check("cts_counters_allreduce_ref", lib().cts_counters_allreduce_ref(E, C, S, n, ctypes.byref(out)))
     return out.as_dict()
 
 
@@ -234,25 +250,71 @@ class Engine:
 
     # ---- verify --------------------------------------------------------------
     def verify(self, arena, descs, *, max_length_hint: int = 0, results=None, counters=None,
-               conn_first_fail=None, stream=None) -> None:
+               conn_first_fail=None, stream=None, base_index: int = 0) -> None:
+        """cts_verify; with a nonzero base_index cts_verify_at: the conn_first_fail slots take base_index + i, the
+        stream ordinal of buffer i, so one slot array serves the launches a connection's stream is cut into."""
         n = _nbytes(descs) // DESC_DTYPE.itemsize
         n_conns = 0 if conn_first_fail is None else _nbytes(conn_first_fail) // 4
         _check_outputs(n, results, counters)
+        if base_index:
+            check("cts_verify_at", self._L.cts_verify_at(self._h, _ptr(arena), _nbytes(arena), _ptr(descs), n,
+                                                       max_length_hint, base_index, _ptr(results), _ptr(counters),
+                                                       _ptr(conn_first_fail), n_conns, _stream(stream)))
+            return
         check("cts_verify", self._L.cts_verify(self._h, _ptr(arena), _nbytes(arena), _ptr(descs), n, max_length_hint,
                                              _ptr(results), _ptr(counters), _ptr(conn_first_fail), n_conns,
                                              _stream(stream)))
 
     def verify_strided(self, arena, stride: int, lengths, *, skip_head: int = 0, expected_offset: int = 0,
-                       conn_index: int = 0, results=None, counters=None, conn_first_fail=None, stream=None) -> None:
+                       conn_index: int = 0, results=None, counters=None, conn_first_fail=None, stream=None,
+                       base_index: int = 0) -> None:
         """cts_verify_strided: buffer i at arena + i * stride, lengths (uint32 device tensor) its completed bytes,
-        one skip / expected offset / connection for the whole ring."""
+        one skip / expected offset / connection for the whole ring. A nonzero base_index (cts_verify_strided_at) is
+        the stream ordinal of buffer 0: the slot takes base_index + i."""
         n = _nbytes(lengths) // 4
         n_conns = 0 if conn_first_fail is None else _nbytes(conn_first_fail) // 4
         _check_outputs(n, results, counters)
+        if base_index:
+            check("cts_verify_strided_at",
+                  self._L.cts_verify_strided_at(self._h, _ptr(arena), _nbytes(arena), stride, _ptr(lengths), n,
+                                                skip_head, expected_offset, conn_index, base_index, _ptr(results),
+                                                _ptr(counters), _ptr(conn_first_fail), n_conns, _stream(stream)))
+            return
         check("cts_verify_strided", self._L.cts_verify_strided(self._h, _ptr(arena), _nbytes(arena), stride,
                                                              _ptr(lengths), n, skip_head, expected_offset, conn_index,
                                                              _ptr(results), _ptr(counters), _ptr(conn_first_fail),
                                                              n_conns, _stream(stream)))
+
+    # ---- the reference view ------------------------------------------------------
+    def refview(self, arena_bytes: int, descs, ref_counters, *, base_index: int = 0, conn_first_fail=None,
+                stream=None) -> None:
+        """cts_refview_accumulate: add the batch's reference view (every connection stopped at its first failing
+        ordinal, conn_first_fail as left by the verifies) to ref_counters, a counter block of its own. Queue it
+        after the verifies that can still lower the batch's slots; it reads descriptors and slots, not the arena."""
+        n = _nbytes(descs) // DESC_DTYPE.itemsize
+        n_conns = 0 if conn_first_fail is None else _nbytes(conn_first_fail) // 4
+        _check_outputs(n, None, ref_counters)
+        check("cts_refview_accumulate",
+              self._L.cts_refview_accumulate(self._h, arena_bytes, _ptr(descs), n, base_index, _ptr(conn_first_fail),
+                                             n_conns, _ptr(ref_counters), _stream(stream)))
+
+    def refview_strided(self, arena_bytes: int, stride: int, lengths, ref_counters, *, skip_head: int = 0,
+                        conn_index: int = 0, base_index: int = 0, conn_first_fail=None, stream=None) -> None:
+        """cts_refview_accumulate_strided: refview over a strided ring's lengths (4 bytes per buffer)."""
+        n = _nbytes(lengths) // 4
+        n_conns = 0 if conn_first_fail is None else _nbytes(conn_first_fail) // 4
+        _check_outputs(n, None, ref_counters)
+        check("cts_refview_accumulate_strided",
+              self._L.cts_refview_accumulate_strided(self._h, arena_bytes, stride, _ptr(lengths), n, skip_head,
+                                                     conn_index, base_index, _ptr(conn_first_fail), n_conns,
+                                                     _ptr(ref_counters), _stream(stream)))
+
+    def read_counters_ref(self, ref_counters, stream=None) -> dict:
+        """cts_counters_read_ref: a reference-view block folded, as cts_counters_ref."""
+        c = CtsCountersRef()
+        check("cts_counters_read_ref", self._L.cts_counters_read_ref(self._h, _ptr(ref_counters), ctypes.byref(c),
+                                                                   _stream(stream)))
+        return c.as_dict()
 
     def new_results(self, n: int):
         return torch.zeros(n * RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda:%d" % self.device)

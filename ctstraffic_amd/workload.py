@@ -199,6 +199,81 @@ def expected_results(w: Workload):
     return first, count, counters, cff
 
 
+REF_FIELDS = ("bytes_recv", "bytes_ok", "buffers_recv", "buffers_failed", "bytes_after_failure",
+              "buffers_after_failure")
+EMPTY_SLOT = 0xFFFFFFFF
+
+
+def descs_bad(descs: np.ndarray, arena_bytes: int) -> np.ndarray:
+    """The verify's bad-descriptor rule (CTS_RESULT_FLAG_BAD_DESC) as a mask: expected offset >= 65536, length below
+    skip_head, or a buffer that leaves the arena."""
+    off = descs["byte_offset"].astype(np.uint64)
+    length = descs["length"].astype(np.uint64)
+    inside = off <= np.uint64(arena_bytes)
+    room = np.where(inside, np.uint64(arena_bytes) - np.where(inside, off, np.uint64(0)), np.uint64(0))
+    return ((descs["expected_pattern_offset"] >= PATTERN_PERIOD) | (descs["length"] < descs["skip_head"]) |
+            ~inside | (room < length))
+
+
+def reference_view(descs: np.ndarray, failed_mask, ordinals, n_conns: int, *, bad=None, slots=None):
+    """The counters as ctsTraffic itself would hold them: a failed VerifyBuffer fails the connection on that
+    completion (ctsIOPattern.cpp:486-489 -> FailedIo), so each connection stops at its first failing ordinal.
+
+    descs: DESC_DTYPE, one per buffer; failed_mask[i]: buffer i did not match; ordinals[i]: its stream ordinal
+    (increasing along each connection's stream; the base_index + i of the launch that held it). ``bad`` marks
+    descriptors the verify refuses (they count nowhere and fail nothing); ``slots`` replaces the first-failure
+    slots derived from failed_mask (uint32[n_conns], 0xFFFFFFFF = empty).
+
+    Returns ({REF_FIELDS: int}, slots uint32[n_conns]): with F the slot of a buffer's connection (empty when the
+    connection has none, conn_index >= n_conns) and g its ordinal, a buffer is received when g <= F, clean when
+    g < F, the failing one when g == F and never received when g > F.
+    """
+    descs = np.asarray(descs)
+    g = np.asarray(ordinals, dtype=np.int64)
+    failed = np.asarray(failed_mask, dtype=bool)
+    live = np.ones(len(descs), dtype=bool) if bad is None else ~np.asarray(bad, dtype=bool)
+    conn = descs["conn_index"].astype(np.int64)
+    has_slot = conn < n_conns
+    if slots is None:
+        slots = np.full(n_conns, EMPTY_SLOT, dtype=np.uint32)
+        pick = failed & live & has_slot
+        np.minimum.at(slots, conn[pick], g[pick].astype(np.uint32))
+    else:
+        slots = np.asarray(slots, dtype=np.uint32)
+        assert slots.shape == (n_conns,)
+    first = np.full(len(descs), EMPTY_SLOT, dtype=np.int64)
+    first[has_slot] = slots[conn[has_slot]].astype(np.int64)
+    vlen = descs["length"].astype(np.int64) - descs["skip_head"].astype(np.int64)
+    recv, ok, at, after = live & (g <= first), live & (g < first), live & (g == first), live & (g > first)
+    sums = {
+        "bytes_recv": int(vlen[recv].sum()),
+        "bytes_ok": int(vlen[ok].sum()),
+        "buffers_recv": int(recv.sum()),
+        "buffers_failed": int(at.sum()),
+        "bytes_after_failure": int(vlen[after].sum()),
+        "buffers_after_failure": int(after.sum()),
+    }
+    return sums, slots
+
+
+def stream_launches(descs: np.ndarray, buffers_per_conn: int, parts: int):
+    """Cut every connection's stream of a connection-major workload (connection_streams) into ``parts`` consecutive
+    pieces: launch k holds piece k of every connection, connection-major, and its base_index is the number of buffers
+    in the launches before it, so a connection's ordinals (base_index + i) increase along its stream.
+
+    Returns [(descs_k, base_index_k, index_k)]: index_k = the positions of the launch's buffers in ``descs``."""
+    n = len(descs)
+    assert n % buffers_per_conn == 0
+    grid = np.arange(n, dtype=np.int64).reshape(-1, buffers_per_conn)
+    cuts = [buffers_per_conn * k // parts for k in range(parts + 1)]
+    out, base = [], 0
+    for k in range(parts):
+        idx = grid[:, cuts[k]:cuts[k + 1]].reshape(-1)
+        out.append((np.ascontiguousarray(descs[idx]), base, idx))
+        base += len(idx)
+    return out
+
+
 def header_bytes(seq: np.ndarray) -> np.ndarray:
     """26-byte MediaStream data headers: u16 flag 0, i64 seq, i64 qpc 0, i64 qpf 0."""
     seq = np.asarray(seq, dtype="<i8")

@@ -116,6 +116,30 @@ typedef struct cts_counters_ex {
     uint64_t connections_failed;
 } cts_counters_ex;
 
+/* The reference view of the same traffic: what ctsTraffic itself would have counted. A failed VerifyBuffer fails
+ * the connection on that completion (ctsIOPattern.cpp:486-489 -> FailedIo), so nothing after a connection's first
+ * failing buffer is received or counted ("as if it had stopped at the first failing buffer").
+ * Accumulated by cts_refview_accumulate into a second device counter block (same size, same shards, same folds) and
+ * read by the *_ref entry points. With g a buffer's stream ordinal and F its connection's first failing ordinal
+ * (0xFFFFFFFF = none), vlen = length - skip_head, bad descriptors excluded:
+ * bytes_recv           : sum of vlen over g <= F (the failing buffer's bytes count: it was received, as
+ *                        cts_pattern_stats.bytes_recv_at_failure counts it); what m_bytesRecv takes
+ * bytes_ok             : sum of vlen over g < F
+ * buffers_recv         : # buffers with g <= F
+ * buffers_failed       : # buffers with g == F, at most one per connection (== connections_failed)
+ * bytes_after_failure  : sum of vlen over g > F: bytes cts_counters.bytes_checked holds and the reference never saw
+ * buffers_after_failure: # buffers with g > F
+ * bytes_recv + bytes_after_failure == bytes_checked and buffers_recv + buffers_after_failure == buffers_checked of
+ * the verifies of the same descriptors. */
+typedef struct cts_counters_ref {
+    uint64_t bytes_recv;
+    uint64_t bytes_ok;
+    uint64_t buffers_recv;
+    uint64_t buffers_failed;
+    uint64_t bytes_after_failure;
+    uint64_t buffers_after_failure;
+} cts_counters_ref;
+
 typedef struct cts_engine cts_engine;
 
 /* ---- library / pattern helpers ------------------------------------------ */
@@ -198,7 +222,10 @@ int cts_fill(cts_engine* engine, void* dev_arena, uint64_t arena_bytes,
  *                           != 0xFFFFFFFF when descriptors of one connection are
  *                           in stream order; with dev_counters given it is also
  *                           accumulated on the device (connections_failed,
- *                           cts_counters_read_ex).
+ *                           cts_counters_read_ex). i is the index inside this launch:
+ *                           when a connection's stream spans several launches over
+ *                           one slot array, use cts_verify_at, whose slots hold
+ *                           stream ordinals and so name the first failing buffer.
  * dev_arena must be 16-byte aligned and its allocation must extend to a
  * multiple of 16 bytes (every hipMalloc allocation does); dev_descs must be
  * 8-byte aligned, dev_results and dev_conn_first_fail 4-byte aligned and
@@ -282,6 +309,53 @@ int cts_verify_strided(cts_engine* engine, const void* dev_arena, uint64_t arena
                        const uint32_t* dev_lengths, uint32_t n, uint32_t skip_head, uint32_t expected_offset,
                        uint32_t conn_index, cts_verify_result* dev_results, void* dev_counters,
                        uint32_t* dev_conn_first_fail, uint32_t n_conns, void* stream);
+
+/* ---- stream ordinals and the reference view ----------------------------------- */
+/* cts_verify / cts_verify_strided with base_index, the stream ordinal of buffer 0 of the launch: for every failing
+ * buffer i of connection c (< n_conns) the kernel does atomicMin(slot[c], base_index + i), and connections_failed is
+ * still claimed by the atomicMin that found 0xFFFFFFFF. Records, counters and everything else use the launch-local
+ * i, as cts_verify does; cts_verify(...) is cts_verify_at(..., base_index = 0, ...).
+ * Contract: over the launches that share a slot array, a connection's buffers get increasing ordinals in its
+ * stream order (later in the stream = larger ordinal); then slot[c] is the ordinal of c's first failing buffer,
+ * whatever order the launches run in. Ordinal 0xFFFFFFFF stays the empty slot, so base_index + n > 0xFFFFFFFF is
+ * CTS_E_INVALID: a slot array lives for 2^32 - 1 ordinals, after which the caller re-initialises it (with the
+ * counter blocks) and starts again from 0. */
+int cts_verify_at(cts_engine* engine, const void* dev_arena, uint64_t arena_bytes, const cts_buf_desc* dev_descs,
+                  uint32_t n, uint32_t max_length_hint, uint32_t base_index, cts_verify_result* dev_results,
+                  void* dev_counters, uint32_t* dev_conn_first_fail, uint32_t n_conns, void* stream);
+int cts_verify_strided_at(cts_engine* engine, const void* dev_arena, uint64_t arena_bytes, uint32_t stride,
+                          const uint32_t* dev_lengths, uint32_t n, uint32_t skip_head, uint32_t expected_offset,
+                          uint32_t conn_index, uint32_t base_index, cts_verify_result* dev_results,
+                          void* dev_counters, uint32_t* dev_conn_first_fail, uint32_t n_conns, void* stream);
+
+/* The reference-view pass: accumulates cts_counters_ref of the n descriptors (ordinals base_index .. base_index +
+ * n - 1, as given to cts_verify_at) into dev_ref_counters, a device counter block of its own
+ * (cts_counters_device_bytes(), cts_counters_reset). It reads the descriptors (24 bytes per buffer; 4 for a strided
+ * ring) and the slots, never the arena; arena_bytes only judges bad descriptors exactly as the verify does (for a
+ * ring also length > stride and a buffer that leaves the arena), and those count nowhere.
+ * Contract:
+ *  - pass each descriptor exactly once (the pass adds; a batch given twice counts twice);
+ *  - the pass must be ordered, by stream order or an event, after every verify launch that can still lower the
+ *    slots of the batch's connections, i.e. every launch holding ordinals <= the batch's own for them. With
+ *    per-connection stream order across launches, "verify batch k, then refview batch k on the same stream" does;
+ *  - a connection with no slot (conn_index >= n_conns) counts as never failing.
+ * dev_conn_first_fail may be NULL only with n_conns == 0. Alignment and null rules, n == 0 and the ordinal limit as
+ * the verify entry points (CTS_E_INVALID). */
+int cts_refview_accumulate(cts_engine* engine, uint64_t arena_bytes, const cts_buf_desc* dev_descs, uint32_t n,
+                           uint32_t base_index, const uint32_t* dev_conn_first_fail, uint32_t n_conns,
+                           void* dev_ref_counters, void* stream);
+int cts_refview_accumulate_strided(cts_engine* engine, uint64_t arena_bytes, uint32_t stride,
+                                   const uint32_t* dev_lengths, uint32_t n, uint32_t skip_head, uint32_t conn_index,
+                                   uint32_t base_index, const uint32_t* dev_conn_first_fail, uint32_t n_conns,
+                                   void* dev_ref_counters, void* stream);
+
+/* The three counter reads over reference-view blocks: the same fold, and for the all-reduce the same ncclAllReduce
+ * of count 6, with the six words named as cts_counters_ref. */
+int cts_counters_read_ref(cts_engine* engine, const void* dev_ref_counters, cts_counters_ref* out, void* stream);
+int cts_counters_read_multi_ref(cts_engine* const* engines, const void* const* dev_ref_counters, void* const* streams,
+                                uint32_t n, cts_counters_ref* out);
+int cts_counters_allreduce_ref(cts_engine* const* engines, const void* const* dev_ref_counters, void* const* streams,
+                               uint32_t n, cts_counters_ref* out);
 
 /* ---- host-buffer drop-in for ctsIoPattern::VerifyBuffer ---------------------- */
 /* Verifies `len` bytes at host_buf against the pattern starting at
