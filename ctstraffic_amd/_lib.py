@@ -36,6 +36,8 @@ CTS_E_TIMEOUT = -6
 PATTERN_PERIOD = 65536
 UDP_DATA_HEADER_LENGTH = 26
 STATUS_ERROR_DATA_DID_NOT_MATCH_BIT_PATTERN = 2147483644  # MAXINT - 3, ctsIOPattern.h:49
+STATUS_ERROR_TOO_MUCH_DATA_TRANSFERRED = 2147483645  # MAXINT - 2, ctsIOPattern.h:48
+STATUS_ERROR_NOT_ALL_DATA_TRANSFERRED = 2147483646  # MAXINT - 1, ctsIOPattern.h:47
 COUNTER_SHARDS = 64
 ATTR_BLOCKS_PER_CU = 1
 ATTR_NT_LOADS = 2
@@ -97,6 +99,21 @@ class CtsCountersRef(ctypes.Structure):
         ("buffers_failed", ctypes.c_uint64),
         ("bytes_after_failure", ctypes.c_uint64),
         ("buffers_after_failure", ctypes.c_uint64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+class CtsCountersClose(ctypes.Structure):
+    """cts_counters_close: the connections closed by cts_conns_close, by class (laid out like cts_counters_ex)."""
+    _fields_ = [
+        ("connections_closed", ctypes.c_uint64),
+        ("successful", ctypes.c_uint64),
+        ("data_errors", ctypes.c_uint64),
+        ("not_all_data", ctypes.c_uint64),
+        ("too_much_data", ctypes.c_uint64),
+        ("bytes_recv", ctypes.c_uint64),
     ]
 
     def as_dict(self) -> dict:
@@ -171,6 +188,15 @@ def _declare(L: ctypes.CDLL) -> None:
                                          ctypes.POINTER(CtsCountersRef)], i32),
         "cts_counters_allreduce_ref": ([ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), u32,
                                         ctypes.POINTER(CtsCountersRef)], i32),
+        "cts_refview_accumulate_conns": ([P, u64, P, u32, u32, P, u32, P, P, P], i32),
+        "cts_refview_accumulate_conns_strided": ([P, u64, u32, P, u32, u32, u32, u32, P, u32, P, P, P], i32),
+        "cts_conns_close": ([P, P, P, u32, P, P, u32, P, P, P], i32),
+        "cts_conn_slots_rebase": ([P, P, u32, u32, P], i32),
+        "cts_counters_read_close": ([P, P, ctypes.POINTER(CtsCountersClose), P], i32),
+        "cts_counters_read_multi_close": ([ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), u32,
+                                           ctypes.POINTER(CtsCountersClose)], i32),
+        "cts_counters_allreduce_close": ([ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), u32,
+                                          ctypes.POINTER(CtsCountersClose)], i32),
         "cts_counters_device_bytes": ([], ctypes.c_size_t),
         "cts_counters_reset": ([P, P, P], i32),
         "cts_counters_read": ([P, P, ctypes.POINTER(CtsCounters), P], i32),

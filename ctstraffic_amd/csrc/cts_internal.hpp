@@ -4,6 +4,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "cts_connections.h"
 #include "cts_engine.h"
 #include "cts_media_stream.h"
 
@@ -158,7 +159,24 @@ hipError_t launch_refview_strided(uint64_t arena_bytes, uint32_t stride, const u
                                   const uint32_t* conn_first_fail, uint32_t n_conns, uint64_t* ref_counters,
                                   hipStream_t stream, const LaunchGeometry& geo);
 
-// The engine's device and launch geometry for the entry points that live outside cts_engine.cpp (cts_refview.cpp);
+// Connections on the device (cts_connections.cpp): the reference-view pass that also adds each buffer's share to its
+// connection's entry, the close of a list of connections, and the slot rebase.
+hipError_t launch_conn_accumulate(uint64_t arena_bytes, const cts_buf_desc* descs, uint32_t n, uint32_t base_index,
+                                  const uint32_t* conn_first_fail, uint32_t n_conns, uint64_t* ref_counters,
+                                  cts_conn_state* conn_state, hipStream_t stream, const LaunchGeometry& geo);
+hipError_t launch_conn_accumulate_strided(uint64_t arena_bytes, uint32_t stride, const uint32_t* lens, uint32_t n,
+                                          uint32_t skip_head, uint32_t conn_index, uint32_t base_index,
+                                          const uint32_t* conn_first_fail, uint32_t n_conns, uint64_t* ref_counters,
+                                          cts_conn_state* conn_state, hipStream_t stream, const LaunchGeometry& geo);
+hipError_t launch_conn_close(const uint32_t* conn_ids, const uint64_t* expected_bytes, uint32_t n,
+                             uint32_t* conn_first_fail, cts_conn_state* conn_state, uint32_t n_conns,
+                             cts_conn_result* results, uint64_t* close_counters, hipStream_t stream,
+                             const LaunchGeometry& geo);
+hipError_t launch_conn_slots_rebase(uint32_t* conn_first_fail, uint32_t n_conns, uint32_t delta, hipStream_t stream,
+                                    const LaunchGeometry& geo);
+
+// The engine's device and launch geometry for the entry points that live outside cts_engine.cpp (cts_refview.cpp,
+// cts_connections.cpp);
 // e != nullptr. Defined in cts_engine.cpp, where cts_engine is complete.
 const LaunchGeometry& engine_geometry(const cts_engine* e, int* device);
 

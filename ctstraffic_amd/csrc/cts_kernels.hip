@@ -23,6 +23,8 @@
 //                                     same body with cts_verify_at's base_index argument
 //   verify_quad_kernel                four buffers per wave (datagram-sized buffers; descriptors or a strided ring)
 //   refview_accumulate                the reference view of a verified batch: descriptors and DataError slots only
+//   conn_accumulate                   the same pass keeping each connection's entry too (runs summed on the chip);
+//                                     conn_close and conn_slots_rebase close, recycle and rebase the connection slots
 //   media_stream_verify_quad_kernel   MediaStream receive: header + payload, four datagrams per wave
 //   fill_kernel / fill_span_kernel / fill_batched_kernel / media_stream_fill_ring_kernel   the sender side
 //   mailbox_kernel                    SYNC-mode VerifyBuffer without a launch per call (resident grid)
@@ -1181,6 +1183,282 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // ---------------------------------------------------------------------------------------------
+// Connections on the device (cts_connections.h): the reference-view pass that also keeps each connection's entry
+// (conn_accumulate), the close (conn_close) and the slot rebase (conn_slots_rebase).
+
+// Six wave-reduced sums (lane 0 of each wave holds them) over the workgroup's waves in LDS, then one add per word to
+// the workgroup's shard of a counter block: the route of flush_counters and of refview_accumulate.
+__device__ __forceinline__ void block_add_six(const uint64_t (&v)[kCounterCount], uint64_t (*red)[kCounterCount],
+                                              uint64_t* __restrict__ block)
+{
+    if ((threadIdx.x & 63u) == 0u) {
+#pragma unroll
+        for (int k = 0; k < kCounterCount; ++k) red[threadIdx.x / 64][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < (unsigned)kCounterCount) {
+        uint64_t sum = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) sum += red[w][threadIdx.x];
+        if (sum)
+            atomicAdd((unsigned long long*)&block[(blockIdx.x % CTS_COUNTER_SHARDS) * kCounterSlots + threadIdx.x],
+                      (unsigned long long)sum);
+    }
+}
+
+// One finished run of a connection's buffers into its entry: at most four 64-bit adds.
+__device__ __forceinline__ void conn_run_add(cts_conn_state* __restrict__ state, uint32_t conn, uint32_t n_conns,
+                                             uint64_t recv, uint64_t after, uint32_t nrecv, uint32_t nafter)
+{
+    if (conn >= n_conns) return;  // a connection without an entry (and kNone, the key of lanes that count nowhere)
+    unsigned long long* p = reinterpret_cast<unsigned long long*>(state + conn);
+    if (recv) atomicAdd(p + 0, (unsigned long long)recv);
+    if (nrecv) atomicAdd(p + 1, (unsigned long long)nrecv);
+    if (after) atomicAdd(p + 2, (unsigned long long)after);
+    if (nafter) atomicAdd(p + 3, (unsigned long long)nafter);
+}
+
+// refview_accumulate plus the per-connection entries. The node-wide six sums take refview_accumulate's route
+// unchanged. The entries would take one set of atomics per buffer, and a strided ring or a connection-major batch
+// sends them all to one 32-byte entry; so everything that shares an entry is summed on the chip first. Each wave
+// walks a contiguous span of the batch (`span` descriptors, a multiple of 64; not a grid-stride interleave), 64
+// descriptors per step, so its loads are still 64 x 24 contiguous bytes and runs of equal conn_index lie in
+// neighbouring lanes. In a tile, a lane whose conn_index differs from the lane below heads a run; the runs are summed
+// by a segmented inclusive scan (shuffles, six steps); the tail lane of every run that ends inside the tile adds it to
+// the entry, and the run that reaches lane 63 is carried in registers into the wave's next tile, where it either goes
+// on (same conn_index in lane 0) or is added by lane 0. The run a wave still holds at the end of its span goes to LDS,
+// where runs that go on across the workgroup's four waves are joined before they are added. A connection's entry
+// therefore takes at most four adds per run and wave, and a one-connection batch 4 x (workgroups in the grid) adds,
+// whatever n is: adds to one address serialise in L2, 32 768 of them (one set per wave, 16 Mi-datagram ring) took
+// about 215 us. Lanes that count nowhere (bad descriptors, the tail of a partial tile) carry the key kNone, which has
+// no entry.
+template <bool NT, bool STRIDED>
+__global__ void __launch_bounds__(kBlock)
+    conn_accumulate(uint64_t arena_bytes, VSource src, uint32_t n, uint32_t base_index,
+                    const uint32_t* __restrict__ conn_first_fail, uint32_t n_conns, uint64_t* __restrict__ ref,
+                    cts_conn_state* __restrict__ state, uint32_t span)
+{
+    __shared__ uint64_t red[kBlock / 64][kCounterCount];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t lo = ((uint64_t)blockIdx.x * (kBlock / 64) + threadIdx.x / 64) * span;
+    const uint64_t hi = lo + span < (uint64_t)n ? lo + span : (uint64_t)n;  // lo >= n: an empty span
+    uint64_t bytes_recv = 0, bytes_ok = 0, bytes_after = 0;
+    uint32_t bufs_recv = 0, bufs_failed = 0, bufs_after = 0;
+    // the open run: the one that reached lane 63 of the previous tile (wave-uniform)
+    __shared__ uint64_t tail_sum[kBlock / 64][4];
+    __shared__ uint32_t tail_key[kBlock / 64][2];
+    uint32_t ckey = kNone, cnrecv = 0, cnafter = 0;
+    uint64_t crecv = 0, cafter = 0;
+    bool whole = true;  // the span so far is one run (wave-uniform)
+    // per-lane sums of the tiles that were nothing but the open run, not yet in crecv .. cnafter
+    uint64_t pa = 0, pb = 0;
+    uint32_t pnrecv = 0, pnafter = 0;
+    bool parked = false;
+    // a ring is one connection: its slot is read once
+    uint32_t ring_first = kNone;
+    if constexpr (STRIDED) ring_first = src.conn_index < n_conns ? conn_first_fail[src.conn_index] : kNone;
+    cts_buf_desc dn = cts_buf_desc{0, 0, 65536u, 0, 0};
+    if (lo < hi) dn = refview_desc<NT, STRIDED>(src, lo + lane < hi ? lo + lane : hi - 1);
+    for (uint64_t t = lo; t < hi; t += 64) {
+        const uint64_t i = t + lane;
+        const cts_buf_desc d = dn;
+        if (t + 64 < hi) dn = refview_desc<NT, STRIDED>(src, i + 64 < hi ? i + 64 : hi - 1);  // the next tile, early
+        const bool ok = i < hi && !desc_bad(d, arena_bytes);
+        const uint32_t key = ok ? d.conn_index : kNone;
+        // a connection without a slot never fails
+        const uint32_t first = STRIDED ? ring_first : (key < n_conns ? conn_first_fail[key] : kNone);
+        const uint32_t g = base_index + (uint32_t)i;  // base_index + n <= 0xFFFFFFFF (checked by the entry point)
+        const uint32_t vlen = ok ? d.length - d.skip_head : 0u;
+        const bool recv = ok && g <= first, after = ok && g > first;
+        if (recv) {
+            bytes_recv += vlen;
+            bufs_recv += 1u;
+            if (g < first) bytes_ok += vlen;
+            else bufs_failed += 1u;
+        } else if (after) {
+            bytes_after += vlen;
+            bufs_after += 1u;
+        }
+        // run heads, and for every lane the head of its run
+        const uint32_t below = (uint32_t)__shfl_up((int)key, 1, 64);
+        const bool head = lane == 0u || key != below;
+        const uint64_t heads = __ballot(head);
+        const uint32_t h = 63u - (uint32_t)__builtin_clzll(heads & (~0ull >> (63u - lane)));
+        const bool merge = (uint32_t)__shfl((int)key, 0, 64) == ckey;
+        if (heads == 1ull && merge) {
+            // the whole tile goes on the open run: per-lane sums, no shuffle (they join the run when it is next needed)
+            pa += recv ? vlen : 0u;
+            pb += after ? vlen : 0u;
+            pnrecv += recv ? 1u : 0u;
+            pnafter += after ? 1u : 0u;
+            parked = true;
+            continue;
+        }
+        if (parked) {
+            crecv += wave_sum64(pa);
+            cafter += wave_sum64(pb);
+            cnrecv += wave_sum(pnrecv);
+            cnafter += wave_sum(pnafter);
+            pa = pb = 0;
+            pnrecv = pnafter = 0;
+            parked = false;
+        }
+        // segmented inclusive scan: bytes received, bytes after failure, the two counts packed (each <= 64)
+        uint64_t a = recv ? vlen : 0u, b = after ? vlen : 0u;
+        uint32_t c = (recv ? 1u : 0u) | (after ? 0x10000u : 0u);
+#pragma unroll
+        for (uint32_t off = 1; off < 64u; off <<= 1) {
+            const uint64_t ua = (uint64_t)__shfl_up((unsigned long long)a, off, 64);
+            const uint64_t ub = (uint64_t)__shfl_up((unsigned long long)b, off, 64);
+            const uint32_t uc = (uint32_t)__shfl_up((int)c, off, 64);
+            if (lane >= h + off) {
+                a += ua;
+                b += ub;
+                c += uc;
+            }
+        }
+        uint32_t nrecv = c & 0xFFFFu, nafter = c >> 16;
+        // the open run goes on in lane 0's run, or ends here
+        whole = whole && heads == 1ull && (merge || t == lo);
+        if (merge && h == 0u) {
+            a += crecv;
+            b += cafter;
+            nrecv += cnrecv;
+            nafter += cnafter;
+        }
+        if (!merge && lane == 0u) conn_run_add(state, ckey, n_conns, crecv, cafter, cnrecv, cnafter);
+        const bool tail = lane == 63u || ((heads >> (lane + 1u)) & 1ull) != 0ull;
+        if (tail && lane != 63u) conn_run_add(state, key, n_conns, a, b, nrecv, nafter);
+        ckey = (uint32_t)__shfl((int)key, 63, 64);
+        crecv = (uint64_t)__shfl((unsigned long long)a, 63, 64);
+        cafter = (uint64_t)__shfl((unsigned long long)b, 63, 64);
+        cnrecv = (uint32_t)__shfl((int)nrecv, 63, 64);
+        cnafter = (uint32_t)__shfl((int)nafter, 63, 64);
+    }
+    // The waves' last open runs meet in LDS: the spans of a workgroup's waves follow one another, so a wave whose
+    // whole span was one run goes on the run the wave before it left open, and a one-connection batch costs four adds
+    // per workgroup.
+    if (parked) {
+        crecv += wave_sum64(pa);
+        cafter += wave_sum64(pb);
+        cnrecv += wave_sum(pnrecv);
+        cnafter += wave_sum(pnafter);
+    }
+    if (lane == 0u) {
+        tail_sum[threadIdx.x / 64][0] = crecv;
+        tail_sum[threadIdx.x / 64][1] = cafter;
+        tail_sum[threadIdx.x / 64][2] = cnrecv;
+        tail_sum[threadIdx.x / 64][3] = cnafter;
+        tail_key[threadIdx.x / 64][0] = ckey;
+        tail_key[threadIdx.x / 64][1] = whole ? 1u : 0u;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint32_t key = tail_key[0][0];
+        uint64_t acc[4] = {tail_sum[0][0], tail_sum[0][1], tail_sum[0][2], tail_sum[0][3]};
+        for (int w = 1; w < kBlock / 64; ++w) {
+            if (tail_key[w][1] == 0u || tail_key[w][0] != key) {
+                conn_run_add(state, key, n_conns, acc[0], acc[1], (uint32_t)acc[2], (uint32_t)acc[3]);
+                key = tail_key[w][0];
+                acc[0] = acc[1] = acc[2] = acc[3] = 0;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[k] += tail_sum[w][k];
+        }
+        conn_run_add(state, key, n_conns, acc[0], acc[1], (uint32_t)acc[2], (uint32_t)acc[3]);
+    }
+    uint64_t v[kCounterCount];
+    v[kRefBytesRecv] = wave_sum64(bytes_recv);
+    v[kRefBytesOk] = wave_sum64(bytes_ok);
+    v[kRefBuffersRecv] = wave_sum(bufs_recv);  // a wave's 64 lanes of one launch: still below 2^32
+    v[kRefBuffersFailed] = wave_sum(bufs_failed);
+    v[kRefBytesAfterFailure] = wave_sum64(bytes_after);
+    v[kRefBuffersAfterFailure] = wave_sum(bufs_after);
+    block_add_six(v, red, ref);
+}
+
+// cts_conns_close: one lane per closed connection. Plain loads of the slot and the entry, the status, the result,
+// then the empty slot and the zero entry; the class counts and the byte sum go to the close block's shard by the
+// route of flush_counters. The ids and the expected sizes are read once (nontemporal with CTS_ATTR_NT_LOADS).
+enum CloseSlot {
+    kCloseClosed = 0,
+    kCloseSuccessful = 1,
+    kCloseDataErrors = 2,
+    kCloseNotAllData = 3,
+    kCloseTooMuchData = 4,
+    kCloseBytesRecv = 5
+};
+static_assert(kCloseBytesRecv + 1 == kCounterCount, "a close block folds like a counter block");
+
+template <bool NT>
+__global__ void __launch_bounds__(kBlock)
+    conn_close(const uint32_t* __restrict__ ids, const uint64_t* __restrict__ expected, uint32_t n,
+               uint32_t* __restrict__ conn_first_fail, cts_conn_state* __restrict__ state, uint32_t n_conns,
+               cts_conn_result* __restrict__ results, uint64_t* __restrict__ block)
+{
+    __shared__ uint64_t red[kBlock / 64][kCounterCount];
+    uint32_t closed = 0, successful = 0, data_errors = 0, not_all = 0, too_much = 0;
+    uint64_t bytes = 0;
+    const uint64_t step = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += step) {
+        const uint32_t c = NT ? __builtin_nontemporal_load(ids + i) : ids[i];
+        cts_conn_result r = cts_conn_result{0, 0, 0, 0, 0u, 0u, c, 0u};
+        if (c >= n_conns) {
+            r.flags = CTS_CONN_RESULT_FLAG_BAD_CONN;
+        } else {
+            const uint32_t first = conn_first_fail[c];
+            const cts_conn_state s = state[c];
+            uint32_t status = 0u;
+            if (first != kNone) {
+                status = CTS_STATUS_ERROR_DATA_DID_NOT_MATCH_BIT_PATTERN;
+                data_errors += 1u;
+            } else if (expected != nullptr) {
+                const uint64_t want = NT ? __builtin_nontemporal_load(expected + i) : expected[i];
+                if (s.bytes_recv > want) {
+                    status = CTS_STATUS_ERROR_TOO_MUCH_DATA_TRANSFERRED;
+                    too_much += 1u;
+                } else if (s.bytes_recv < want) {
+                    status = CTS_STATUS_ERROR_NOT_ALL_DATA_TRANSFERRED;
+                    not_all += 1u;
+                }
+            }
+            if (status == 0u) successful += 1u;
+            closed += 1u;
+            bytes += s.bytes_recv;
+            r.bytes_recv = s.bytes_recv;
+            r.buffers_recv = s.buffers_recv;
+            r.bytes_after_failure = s.bytes_after_failure;
+            r.buffers_after_failure = s.buffers_after_failure;
+            r.first_fail = first;
+            r.status = status;
+            // the slot's next connection starts fresh
+            conn_first_fail[c] = kNone;
+            state[c] = cts_conn_state{0, 0, 0, 0};
+        }
+        if (results != nullptr) results[i] = r;
+    }
+    uint64_t v[kCounterCount];
+    v[kCloseClosed] = wave_sum(closed);  // fewer than 2^32 ids per launch
+    v[kCloseSuccessful] = wave_sum(successful);
+    v[kCloseDataErrors] = wave_sum(data_errors);
+    v[kCloseNotAllData] = wave_sum(not_all);
+    v[kCloseTooMuchData] = wave_sum(too_much);
+    v[kCloseBytesRecv] = wave_sum64(bytes);
+    block_add_six(v, red, block);
+}
+
+// cts_conn_slots_rebase: one lane per slot, grid-stride. F -> F - delta, clamped at 0; empty slots stay empty.
+__global__ void __launch_bounds__(kBlock) conn_slots_rebase(uint32_t* __restrict__ conn_first_fail, uint32_t n_conns,
+                                                            uint32_t delta)
+{
+    const uint64_t step = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n_conns; i += step) {
+        const uint32_t first = conn_first_fail[i];
+        if (first != kNone) conn_first_fail[i] = first < delta ? 0u : first - delta;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // fill: the write-bound twin. Interior chunks are 16-byte stores; the (at most
 // two) edge chunks of a span write only their own bytes, so neighbouring buffers
 // sharing a 16-byte line are never touched.
@@ -2324,6 +2602,78 @@ hipError_t launch_refview_strided(uint64_t arena_bytes, uint32_t stride, const u
     // expected offset 0: the pass reads no pattern, the field only carries vs_desc's length > stride rule
     return launch_refview_src<true>(arena_bytes, VSource{nullptr, lens, stride, skip_head, 0u, conn_index}, n,
                                     base_index, conn_first_fail, n_conns, ref_counters, stream, geo);
+}
+
+// cts_refview_accumulate_conns(_strided): refview's grid; every wave of it takes one contiguous span of the batch, a
+// multiple of 64 descriptors
+template <bool STRIDED>
+static hipError_t launch_conn_accumulate_src(uint64_t arena_bytes, const VSource& src, uint32_t n, uint32_t base_index,
+                                             const uint32_t* conn_first_fail, uint32_t n_conns, uint64_t* ref_counters,
+                                             cts_conn_state* conn_state, hipStream_t stream, const LaunchGeometry& geo)
+{
+    if (n == 0) return hipSuccess;
+    const uint64_t want = ((uint64_t)n + kBlock - 1) / kBlock;
+    const uint64_t cap = (uint64_t)(geo.num_cus > 0 ? geo.num_cus : 1) * kRefviewBlocksPerCu;
+    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    const uint64_t waves = (uint64_t)grid * (kBlock / 64);
+    const uint32_t span = (uint32_t)((((uint64_t)n + waves - 1) / waves + 63u) / 64u * 64u);
+    if (geo.nontemporal)
+        conn_accumulate<true, STRIDED><<<grid, kBlock, 0, stream>>>(arena_bytes, src, n, base_index, conn_first_fail,
+                                                                    n_conns, ref_counters, conn_state, span);
+    else
+        conn_accumulate<false, STRIDED><<<grid, kBlock, 0, stream>>>(arena_bytes, src, n, base_index, conn_first_fail,
+                                                                     n_conns, ref_counters, conn_state, span);
+    return hipGetLastError();
+}
+
+hipError_t launch_conn_accumulate(uint64_t arena_bytes, const cts_buf_desc* descs, uint32_t n, uint32_t base_index,
+                                  const uint32_t* conn_first_fail, uint32_t n_conns, uint64_t* ref_counters,
+                                  cts_conn_state* conn_state, hipStream_t stream, const LaunchGeometry& geo)
+{
+    return launch_conn_accumulate_src<false>(arena_bytes, VSource{descs, nullptr, 0u, 0u, 0u, 0u}, n, base_index,
+                                             conn_first_fail, n_conns, ref_counters, conn_state, stream, geo);
+}
+
+hipError_t launch_conn_accumulate_strided(uint64_t arena_bytes, uint32_t stride, const uint32_t* lens, uint32_t n,
+                                          uint32_t skip_head, uint32_t conn_index, uint32_t base_index,
+                                          const uint32_t* conn_first_fail, uint32_t n_conns, uint64_t* ref_counters,
+                                          cts_conn_state* conn_state, hipStream_t stream, const LaunchGeometry& geo)
+{
+    return launch_conn_accumulate_src<true>(arena_bytes, VSource{nullptr, lens, stride, skip_head, 0u, conn_index}, n,
+                                            base_index, conn_first_fail, n_conns, ref_counters, conn_state, stream,
+                                            geo);
+}
+
+// one lane per id (cts_conns_close) or per slot (cts_conn_slots_rebase), grid-stride beyond refview's grid cap
+static inline uint32_t lane_per_item_grid(uint32_t n, const LaunchGeometry& geo)
+{
+    const uint64_t want = ((uint64_t)n + kBlock - 1) / kBlock;
+    const uint64_t cap = (uint64_t)(geo.num_cus > 0 ? geo.num_cus : 1) * kRefviewBlocksPerCu;
+    return (uint32_t)(want < cap ? want : cap);
+}
+
+hipError_t launch_conn_close(const uint32_t* conn_ids, const uint64_t* expected_bytes, uint32_t n,
+                             uint32_t* conn_first_fail, cts_conn_state* conn_state, uint32_t n_conns,
+                             cts_conn_result* results, uint64_t* close_counters, hipStream_t stream,
+                             const LaunchGeometry& geo)
+{
+    if (n == 0) return hipSuccess;
+    const uint32_t grid = lane_per_item_grid(n, geo);
+    if (geo.nontemporal)
+        conn_close<true><<<grid, kBlock, 0, stream>>>(conn_ids, expected_bytes, n, conn_first_fail, conn_state, n_conns,
+                                                      results, close_counters);
+    else
+        conn_close<false><<<grid, kBlock, 0, stream>>>(conn_ids, expected_bytes, n, conn_first_fail, conn_state,
+                                                       n_conns, results, close_counters);
+    return hipGetLastError();
+}
+
+hipError_t launch_conn_slots_rebase(uint32_t* conn_first_fail, uint32_t n_conns, uint32_t delta, hipStream_t stream,
+                                    const LaunchGeometry& geo)
+{
+    if (n_conns == 0 || delta == 0) return hipSuccess;
+    conn_slots_rebase<<<lane_per_item_grid(n_conns, geo), kBlock, 0, stream>>>(conn_first_fail, n_conns, delta);
+    return hipGetLastError();
 }
 
 // grid of the batched datagram fills: whole batches per workgroup, at most ring_fill_blocks_per_cu per CU

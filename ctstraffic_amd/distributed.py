@@ -21,6 +21,10 @@ COUNTER_SLOTS = 8  # u64 per 64-byte counter shard (cts_internal.hpp kCounterSlo
 # stopped at its first failing buffer, as ctsTraffic counts (ctsIOPattern.cpp:486-489)
 REF_FIELDS = ("bytes_recv", "bytes_ok", "buffers_recv", "buffers_failed", "bytes_after_failure",
               "buffers_after_failure")
+# the six words of a close block (cts_counters_close, accumulated by Engine.conns_close): the connections closed, by
+# class; successful and data_errors + not_all_data + too_much_data are the status line's Completed and DataError
+# (ctsSocketState.cpp:221-228)
+CLOSE_FIELDS = ("connections_closed", "successful", "data_errors", "not_all_data", "too_much_data", "bytes_recv")
 
 
 def dist_env():
@@ -66,8 +70,9 @@ def new_cpu_group(timeout_s: Optional[float] = DEFAULT_TIMEOUT_S):
 def fold_counters(counter_block, fields=COUNTER_FIELDS):
     """Device counter block (CTS_COUNTER_SHARDS x 8 int64, cts_counters_device_bytes) -> int64[len(fields)], on the
     block's own device (no host round trip). fields=COUNTER_FIELDS_EX adds the DataError count (connections_failed,
-    counted by the verifies given a conn_first_fail array); fields=REF_FIELDS folds a reference-view block."""
-    assert tuple(fields) in (COUNTER_FIELDS_EX[: len(fields)], REF_FIELDS), fields
+    counted by the verifies given a conn_first_fail array); fields=REF_FIELDS folds a reference-view block and
+    fields=CLOSE_FIELDS a close block."""
+    assert tuple(fields) in (COUNTER_FIELDS_EX[: len(fields)], REF_FIELDS, CLOSE_FIELDS), fields
     return counter_block.view(-1, COUNTER_SLOTS)[:, : len(fields)].sum(0)
 
 
@@ -125,5 +130,5 @@ def gather_rank_rows(row, group=None) -> list:
     return [r.tolist() for r in rows]
 
 
-__all__ = ["dist_env", "init", "new_cpu_group", "DEFAULT_TIMEOUT_S", "REF_FIELDS", "fold_counters", "allreduce_counters", "counters_dict", "max_over_ranks",
+__all__ = ["dist_env", "init", "new_cpu_group", "DEFAULT_TIMEOUT_S", "REF_FIELDS", "CLOSE_FIELDS", "fold_counters", "allreduce_counters", "counters_dict", "max_over_ranks",
            "data_error_count", "gather_rank_rows"]

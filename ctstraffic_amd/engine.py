@@ -12,8 +12,9 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import CtsAllreduceSetup, CtsCounters, CtsCountersEx, CtsCountersRef, CtsVerifyResult, check, lib
-from .types import DESC_DTYPE, RESULT_DTYPE
+from ._lib import (CtsAllreduceSetup, CtsCounters, CtsCountersClose, CtsCountersEx, CtsCountersRef, CtsVerifyResult,
+                   check, lib)
+from .types import CONN_RESULT_DTYPE, CONN_STATE_DTYPE, DESC_DTYPE, RESULT_DTYPE
 
 try:
     import torch
@@ -137,6 +138,22 @@ def counters_allreduce_ref(engines: Sequence["Engine"], blocks, streams=None) ->
     E, C, S, n = _multi_args(engines, blocks, streams)
     out = CtsCountersRef()
     check("cts_counters_allreduce_ref", lib().cts_counters_allreduce_ref(E, C, S, n, ctypes.byref(out)))
+    return out.as_dict()
+
+
+def counters_read_multi_close(engines: Sequence["Engine"], blocks, streams=None) -> dict:
+    """cts_counters_read_multi_close: the node-wide close counts (Engine.conns_close blocks), folded on the host."""
+    E, C, S, n = _multi_args(engines, blocks, streams)
+    out = CtsCountersClose()
+    check("cts_counters_read_multi_close", lib().cts_counters_read_multi_close(E, C, S, n, ctypes.byref(out)))
+    return out.as_dict()
+
+
+def counters_allreduce_close(engines: Sequence["Engine"], blocks, streams=None) -> dict:
+    """cts_counters_allreduce_close: the node-wide close counts reduced on the GPUs (the same u64 x 6 over RCCL)."""
+    E, C, S, n = _multi_args(engines, blocks, streams)
+    out = CtsCountersClose()
+    check("cts_counters_allreduce_close", lib().cts_counters_allreduce_close(E, C, S, n, ctypes.byref(out)))
     return out.as_dict()
 
 
@@ -314,6 +331,80 @@ class Engine:
         c = CtsCountersRef()
         check("cts_counters_read_ref", self._L.cts_counters_read_ref(self._h, _ptr(ref_counters), ctypes.byref(c),
                                                                    _stream(stream)))
+        return c.as_dict()
+
+    # ---- connections on the device (include/cts_connections.h) ----------------------
+    def new_conn_state(self, n_conns: int):
+        """n_conns zeroed cts_conn_state entries (32 bytes each, four int64): every slot a fresh connection."""
+        return torch.zeros(n_conns * (CONN_STATE_DTYPE.itemsize // 8), dtype=torch.int64,
+                           device="cuda:%d" % self.device)
+
+    @staticmethod
+    def _conn_tables(conn_first_fail, conn_state) -> int:
+        """n_conns of a slot array and its entry table; the C ABI cannot see that the table is as long."""
+        n_conns = 0 if conn_first_fail is None else _nbytes(conn_first_fail) // 4
+        have = 0 if conn_state is None else _nbytes(conn_state) // CONN_STATE_DTYPE.itemsize
+        if have < n_conns:
+            raise ValueError("conn_state holds %d entries, conn_first_fail %d slots" % (have, n_conns))
+        return n_conns
+
+    def refview_conns(self, arena_bytes: int, descs, ref_counters, conn_state, *, base_index: int = 0,
+                      conn_first_fail=None, stream=None) -> None:
+        """cts_refview_accumulate_conns: refview, and in the same pass each buffer's share added to its connection's
+        entry of conn_state (new_conn_state)."""
+        n = _nbytes(descs) // DESC_DTYPE.itemsize
+        n_conns = self._conn_tables(conn_first_fail, conn_state)
+        _check_outputs(n, None, ref_counters)
+        check("cts_refview_accumulate_conns",
+              self._L.cts_refview_accumulate_conns(self._h, arena_bytes, _ptr(descs), n, base_index,
+                                                   _ptr(conn_first_fail), n_conns, _ptr(ref_counters),
+                                                   _ptr(conn_state), _stream(stream)))
+
+    def refview_conns_strided(self, arena_bytes: int, stride: int, lengths, ref_counters, conn_state, *,
+                              skip_head: int = 0, conn_index: int = 0, base_index: int = 0, conn_first_fail=None,
+                              stream=None) -> None:
+        """cts_refview_accumulate_conns_strided: refview_conns over a strided ring's lengths."""
+        n = _nbytes(lengths) // 4
+        n_conns = self._conn_tables(conn_first_fail, conn_state)
+        _check_outputs(n, None, ref_counters)
+        check("cts_refview_accumulate_conns_strided",
+              self._L.cts_refview_accumulate_conns_strided(self._h, arena_bytes, stride, _ptr(lengths), n, skip_head,
+                                                           conn_index, base_index, _ptr(conn_first_fail), n_conns,
+                                                           _ptr(ref_counters), _ptr(conn_state), _stream(stream)))
+
+    def conns_close(self, conn_ids, expected_bytes, conn_first_fail, conn_state, close_counters, *, results=None,
+                    stream=None) -> None:
+        """cts_conns_close: classify and report the connections conn_ids (uint32 device tensor, distinct) against
+        expected_bytes (uint64 per id, or None: no byte-count check), add them to the close block, and empty their
+        slots and entries for the next connections. results: None or 48 bytes per id (CONN_RESULT_DTYPE)."""
+        n = _nbytes(conn_ids) // 4
+        n_conns = self._conn_tables(conn_first_fail, conn_state)
+        _check_outputs(0, None, close_counters)
+        if expected_bytes is not None and _nbytes(expected_bytes) < 8 * n:
+            raise ValueError("expected_bytes holds %d bytes, %d ids need %d" % (_nbytes(expected_bytes), n, 8 * n))
+        if results is not None and _nbytes(results) < n * CONN_RESULT_DTYPE.itemsize:
+            raise ValueError("results holds %d bytes, %d ids need %d" % (_nbytes(results), n,
+                                                                         n * CONN_RESULT_DTYPE.itemsize))
+        check("cts_conns_close",
+              self._L.cts_conns_close(self._h, _ptr(conn_ids), _ptr(expected_bytes), n, _ptr(conn_first_fail),
+                                      _ptr(conn_state), n_conns, _ptr(results), _ptr(close_counters),
+                                      _stream(stream)))
+
+    def new_conn_results(self, n: int):
+        return torch.zeros(n * (CONN_RESULT_DTYPE.itemsize // 8), dtype=torch.int64, device="cuda:%d" % self.device)
+
+    def slots_rebase(self, conn_first_fail, delta: int, stream=None) -> None:
+        """cts_conn_slots_rebase: every non-empty slot F becomes max(F - delta, 0); subtract delta from the next
+        base_index."""
+        check("cts_conn_slots_rebase",
+              self._L.cts_conn_slots_rebase(self._h, _ptr(conn_first_fail), _nbytes(conn_first_fail) // 4, delta,
+                                            _stream(stream)))
+
+    def read_counters_close(self, close_counters, stream=None) -> dict:
+        """cts_counters_read_close: a close block folded, as cts_counters_close."""
+        c = CtsCountersClose()
+        check("cts_counters_read_close", self._L.cts_counters_read_close(self._h, _ptr(close_counters),
+                                                                       ctypes.byref(c), _stream(stream)))
         return c.as_dict()
 
     def new_results(self, n: int):

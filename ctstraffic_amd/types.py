@@ -55,3 +55,29 @@ assert DGRAM_STATUS_DTYPE.itemsize == 16
 DGRAM_HEADER_DTYPE = np.dtype([("sequence_number", "<i8"), ("qpc", "<i8"), ("qpf", "<i8")])
 RESULT_FLAG_NOT_DATA = 0x2
 assert DGRAM_RECORD_DTYPE.itemsize == 32 and DGRAM_HEADER_DTYPE.itemsize == 24
+# cts_conn_state (include/cts_connections.h): one connection's share of the reference view; all-zero = fresh
+CONN_STATE_DTYPE = np.dtype(
+    [
+        ("bytes_recv", "<u8"),
+        ("buffers_recv", "<u8"),
+        ("bytes_after_failure", "<u8"),
+        ("buffers_after_failure", "<u8"),
+    ]
+)
+# cts_conn_result: what cts_conns_close reports for one connection
+CONN_RESULT_DTYPE = np.dtype(
+    [
+        ("bytes_recv", "<u8"),
+        ("buffers_recv", "<u8"),
+        ("bytes_after_failure", "<u8"),
+        ("buffers_after_failure", "<u8"),
+        ("first_fail", "<u4"),
+        ("status", "<u4"),
+        ("conn_index", "<u4"),
+        ("flags", "<u4"),
+    ]
+)
+CONN_RESULT_FLAG_BAD_CONN = 0x1
+# cts_counters_close: the six words of a close block
+CLOSE_FIELDS = ("connections_closed", "successful", "data_errors", "not_all_data", "too_much_data", "bytes_recv")
+assert CONN_STATE_DTYPE.itemsize == 32 and CONN_RESULT_DTYPE.itemsize == 48

@@ -256,6 +256,84 @@ def reference_view(descs: np.ndarray, failed_mask, ordinals, n_conns: int, *, ba
     return sums, slots
 
 
+CLOSE_FIELDS = ("connections_closed", "successful", "data_errors", "not_all_data", "too_much_data", "bytes_recv")
+STATUS_ERROR_DATA_DID_NOT_MATCH_BIT_PATTERN = 2147483644  # ctsIOPattern.h:46-50
+STATUS_ERROR_TOO_MUCH_DATA_TRANSFERRED = 2147483645
+STATUS_ERROR_NOT_ALL_DATA_TRANSFERRED = 2147483646
+
+
+def connection_view(descs: np.ndarray, failed_mask, ordinals, n_conns: int, bad=None, slots=None):
+    """reference_view per connection: the table cts_refview_accumulate_conns keeps (include/cts_connections.h).
+
+    Arguments as reference_view. Returns (CONN_STATE_DTYPE[n_conns], slots uint32[n_conns]): entry c holds the bytes
+    and buffers of connection c with g <= F (received) and with g > F (after its failure). Buffers of connections
+    without a slot (conn_index >= n_conns) are in no entry, bad descriptors nowhere; the column sums equal
+    reference_view's bytes_recv, buffers_recv, bytes_after_failure and buffers_after_failure when every connection has
+    a slot."""
+    from .types import CONN_STATE_DTYPE
+
+    descs = np.asarray(descs)
+    g = np.asarray(ordinals, dtype=np.int64)
+    _, slots = reference_view(descs, failed_mask, ordinals, n_conns, bad=bad, slots=slots)
+    live = np.ones(len(descs), dtype=bool) if bad is None else ~np.asarray(bad, dtype=bool)
+    conn = descs["conn_index"].astype(np.int64)
+    live &= conn < n_conns
+    conn, g = conn[live], g[live]
+    vlen = (descs["length"].astype(np.int64) - descs["skip_head"].astype(np.int64))[live]
+    recv = g <= slots[conn].astype(np.int64)
+    table = np.zeros(n_conns, dtype=CONN_STATE_DTYPE)
+    for sel, fb, fn in ((recv, "bytes_recv", "buffers_recv"), (~recv, "bytes_after_failure", "buffers_after_failure")):
+        np.add.at(table[fb], conn[sel], vlen[sel].astype(np.uint64))
+        table[fn] = np.bincount(conn[sel], minlength=n_conns).astype(np.uint64)
+    return table, slots
+
+
+def close_results(state: np.ndarray, slots: np.ndarray, conn_ids, expected_bytes):
+    """cts_conns_close as a model: close the distinct connections conn_ids of a table (connection_view) and its slots
+    against expected_bytes (one per id; None = no byte-count check).
+
+    Returns (CONN_RESULT_DTYPE[len(conn_ids)], {CLOSE_FIELDS: int}, state after, slots after). The data error wins
+    over the byte-count errors; an id >= len(slots) is flagged, counted nowhere and resets nothing."""
+    from .types import CONN_RESULT_DTYPE, CONN_RESULT_FLAG_BAD_CONN
+
+    ids = np.asarray(conn_ids, dtype=np.int64)
+    assert len(np.unique(ids)) == len(ids)
+    state, slots = np.array(state, copy=True), np.array(slots, dtype=np.uint32, copy=True)
+    res = np.zeros(len(ids), dtype=CONN_RESULT_DTYPE)
+    res["conn_index"] = ids
+    good = ids < len(slots)
+    res["flags"][~good] = CONN_RESULT_FLAG_BAD_CONN
+    c = ids[good]
+    for f in state.dtype.names:
+        res[f][good] = state[f][c]
+    res["first_fail"][good] = slots[c]
+    got = state["bytes_recv"][c]
+    status = np.zeros(len(c), dtype=np.uint32)
+    if expected_bytes is not None:
+        want = np.asarray(expected_bytes, dtype=np.uint64)[good]
+        status[got < want] = STATUS_ERROR_NOT_ALL_DATA_TRANSFERRED
+        status[got > want] = STATUS_ERROR_TOO_MUCH_DATA_TRANSFERRED
+    status[slots[c] != EMPTY_SLOT] = STATUS_ERROR_DATA_DID_NOT_MATCH_BIT_PATTERN
+    res["status"][good] = status
+    counts = {
+        "connections_closed": int(len(c)),
+        "successful": int((status == 0).sum()),
+        "data_errors": int((status == STATUS_ERROR_DATA_DID_NOT_MATCH_BIT_PATTERN).sum()),
+        "not_all_data": int((status == STATUS_ERROR_NOT_ALL_DATA_TRANSFERRED).sum()),
+        "too_much_data": int((status == STATUS_ERROR_TOO_MUCH_DATA_TRANSFERRED).sum()),
+        "bytes_recv": int(got.astype(np.uint64).sum()),
+    }
+    slots[c] = EMPTY_SLOT
+    state[c] = 0
+    return res, counts, state, slots
+
+
+def rebase_slots(slots: np.ndarray, delta: int) -> np.ndarray:
+    """cts_conn_slots_rebase as a model: non-empty slots drop by delta, clamped at 0; empty slots stay empty."""
+    s = np.asarray(slots, dtype=np.uint32).astype(np.int64)
+    return np.where(s == EMPTY_SLOT, EMPTY_SLOT, np.maximum(s - int(delta), 0)).astype(np.uint32)
+
+
 def stream_launches(descs: np.ndarray, buffers_per_conn: int, parts: int):
     """Cut every connection's stream of a connection-major workload (connection_streams) into ``parts`` consecutive
     pieces: launch k holds piece k of every connection, connection-major, and its base_index is the number of buffers

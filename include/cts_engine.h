@@ -102,11 +102,16 @@ typedef struct cts_counters {
 } cts_counters;
 
 /* cts_counters plus the DataError count, read by the *_ex entry points (cts_counters keeps its size and meaning).
- * connections_failed: # connections with a failing buffer, i.e. the ConnectionStatusDetails.m_protocolErrorCount
- * increments of ctsSocketState.cpp:221-228 (one per connection whose verify failed, however many of its buffers
- * did). Counted on the device when a verify's atomicMin on dev_conn_first_fail[c] finds the slot still
- * 0xFFFFFFFF, so it counts only in launches given a dev_conn_first_fail array, once per slot over the life of
- * that array (re-initialise the slots when the counter block is reset). */
+ * connections_failed: # connections with a failing buffer (one per connection whose verify failed, however many
+ * of its buffers did): the data-mismatch subset (c_statusErrorDataDidNotMatchBitPattern) of the
+ * ConnectionStatusDetails.m_protocolErrorCount increments of ctsSocketState.cpp:221-228. The other two protocol
+ * errors of IsProtocolError (ctsIOPattern.h:55-58), not-all-data and too-much-data transferred, are judged when a
+ * connection closes and counted in cts_counters_close (cts_connections.h, cts_conns_close), whose data_errors +
+ * not_all_data + too_much_data is the whole m_protocolErrorCount. Counted on the device when a verify's atomicMin on
+ * dev_conn_first_fail[c] finds the slot still 0xFFFFFFFF, so it counts only in launches given a
+ * dev_conn_first_fail array, once per emptying of a slot: cts_conns_close empties the slots it closes, one
+ * connection at a time, and a slot's next connection counts again (or re-initialise all slots when the counter
+ * block is reset). */
 typedef struct cts_counters_ex {
     uint64_t bytes_checked;
     uint64_t bytes_ok;
@@ -319,7 +324,8 @@ int cts_verify_strided(cts_engine* engine, const void* dev_arena, uint64_t arena
  * stream order (later in the stream = larger ordinal); then slot[c] is the ordinal of c's first failing buffer,
  * whatever order the launches run in. Ordinal 0xFFFFFFFF stays the empty slot, so base_index + n > 0xFFFFFFFF is
  * CTS_E_INVALID: a slot array lives for 2^32 - 1 ordinals, after which the caller re-initialises it (with the
- * counter blocks) and starts again from 0. */
+ * counter blocks) and starts again from 0, unless it rebases the slots in time (cts_conn_slots_rebase,
+ * cts_connections.h), which keeps the array and the counters alive. */
 int cts_verify_at(cts_engine* engine, const void* dev_arena, uint64_t arena_bytes, const cts_buf_desc* dev_descs,
                   uint32_t n, uint32_t max_length_hint, uint32_t base_index, cts_verify_result* dev_results,
                   void* dev_counters, uint32_t* dev_conn_first_fail, uint32_t n_conns, void* stream);
