@@ -120,6 +120,22 @@ class CtsCountersClose(ctypes.Structure):
         return {f: int(getattr(self, f)) for f, _ in self._fields_}
 
 
+class CtsCountersUdp(ctypes.Structure):
+    """cts_counters_udp: the node-wide UdpStatusDetails the MediaStream connections feed, plus the datagrams completed
+    (laid out like cts_counters_ex)."""
+    _fields_ = [
+        ("bits_received", ctypes.c_uint64),
+        ("successful_frames", ctypes.c_uint64),
+        ("dropped_frames", ctypes.c_uint64),
+        ("duplicate_frames", ctypes.c_uint64),
+        ("error_frames", ctypes.c_uint64),
+        ("datagrams", ctypes.c_uint64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
 class CtsAllreduceSetup(ctypes.Structure):
     """cts_allreduce_setup: where the newest RCCL clique's set-up time went (ms)."""
     _fields_ = [
@@ -197,6 +213,16 @@ def _declare(L: ctypes.CDLL) -> None:
                                            ctypes.POINTER(CtsCountersClose)], i32),
         "cts_counters_allreduce_close": ([ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), u32,
                                           ctypes.POINTER(CtsCountersClose)], i32),
+        "cts_ms_conn_init": ([P, u64, P], i32),
+        "cts_media_stream_verify_status_at": ([P, P, u64, P, u32, u32, P, P, P, u32, P], i32),
+        "cts_media_stream_conns_accumulate": ([P, u64, P, P, u32, u32, P, P, P, u64, u32, P, P], i32),
+        "cts_media_stream_conns_render": ([P, P, u32, P, P, u32, P, P, P], i32),
+        "cts_media_stream_conns_close": ([P, P, u32, P, P, P, u32, P, P, P], i32),
+        "cts_counters_read_udp": ([P, P, ctypes.POINTER(CtsCountersUdp), P], i32),
+        "cts_counters_read_multi_udp": ([ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), u32,
+                                         ctypes.POINTER(CtsCountersUdp)], i32),
+        "cts_counters_allreduce_udp": ([ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), u32,
+                                        ctypes.POINTER(CtsCountersUdp)], i32),
         "cts_counters_device_bytes": ([], ctypes.c_size_t),
         "cts_counters_reset": ([P, P, P], i32),
         "cts_counters_read": ([P, P, ctypes.POINTER(CtsCounters), P], i32),

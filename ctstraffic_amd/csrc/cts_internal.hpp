@@ -7,6 +7,7 @@
 #include "cts_connections.h"
 #include "cts_engine.h"
 #include "cts_media_stream.h"
+#include "cts_media_stream_conns.h"
 
 namespace cts {
 
@@ -175,8 +176,27 @@ hipError_t launch_conn_close(const uint32_t* conn_ids, const uint64_t* expected_
 hipError_t launch_conn_slots_rebase(uint32_t* conn_first_fail, uint32_t n_conns, uint32_t delta, hipStream_t stream,
                                     const LaunchGeometry& geo);
 
+// MediaStream connections on the device (cts_media_stream_conns.cpp): the status-form receive pass over descriptors
+// that lowers the first-failure slots, the accounting pass over descriptors and statuses, the render tick and the
+// close.
+hipError_t launch_media_stream_status_at(const uint8_t* arena, uint64_t arena_bytes, const cts_buf_desc* descs,
+                                        uint32_t n, uint32_t base_index, cts_datagram_status* status,
+                                        uint64_t* counters, uint32_t* conn_first_fail, uint32_t n_conns,
+                                        hipStream_t stream, const LaunchGeometry& geo);
+hipError_t launch_ms_conn_accumulate(const cts_buf_desc* descs, const cts_datagram_status* status, uint32_t n,
+                                     uint32_t base_index, const uint32_t* conn_first_fail, cts_ms_conn_state* conns,
+                                     uint64_t* frame_bytes, uint64_t frame_elems, uint32_t n_conns,
+                                     uint64_t* udp_counters, hipStream_t stream, const LaunchGeometry& geo);
+hipError_t launch_ms_conn_render(const uint32_t* conn_ids, uint32_t n, cts_ms_conn_state* conns, uint64_t* frame_bytes,
+                                 uint32_t n_conns, uint64_t* udp_counters, uint32_t* codes, hipStream_t stream,
+                                 const LaunchGeometry& geo);
+hipError_t launch_ms_conn_close(const uint32_t* conn_ids, uint32_t n, uint32_t* conn_first_fail,
+                                cts_ms_conn_state* conns, uint64_t* frame_bytes, uint32_t n_conns,
+                                cts_ms_conn_result* results, uint64_t* close_counters, hipStream_t stream,
+                                const LaunchGeometry& geo);
+
 // The engine's device and launch geometry for the entry points that live outside cts_engine.cpp (cts_refview.cpp,
-// cts_connections.cpp);
+// cts_connections.cpp, cts_media_stream_conns.cpp);
 // e != nullptr. Defined in cts_engine.cpp, where cts_engine is complete.
 const LaunchGeometry& engine_geometry(const cts_engine* e, int* device);
 

@@ -1459,6 +1459,369 @@ __global__ void __launch_bounds__(kBlock) conn_slots_rebase(uint32_t* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------
+// MediaStream connections on the device (cts_media_stream_conns.h): the accounting pass over a batch's descriptors
+// and statuses (ms_conn_accumulate), the render tick (ms_conn_render) and the close (ms_conn_close). The receive pass
+// that lowers the slots is ms_verify_status_ordinal, beside the MediaStream receive kernels below.
+enum UdpSlot {
+    kUdpBits = 0,
+    kUdpSuccessful = 1,
+    kUdpDropped = 2,
+    kUdpDuplicate = 3,
+    kUdpErrorFrames = 4,
+    kUdpDatagrams = 5
+};
+static_assert(kUdpDatagrams + 1 == kCounterCount, "a UDP block folds like a counter block");
+
+// What the accounting pass reads of one datagram: its connection (the descriptor's third 8 bytes) and its status.
+struct MsMeta {
+    uint32_t conn;
+    int64_t seq;
+    uint32_t completed;
+    uint32_t fkp;  // flag | kind << 16 | pass << 24
+};
+
+template <bool NT>
+__device__ __forceinline__ MsMeta ms_meta(const cts_buf_desc* __restrict__ descs,
+                                          const cts_datagram_status* __restrict__ status, uint64_t i)
+{
+    const uint64_t* dp = reinterpret_cast<const uint64_t*>(descs + i) + 2;
+    const uint64_t* sp = reinterpret_cast<const uint64_t*>(status + i);
+    const uint64_t c = NT ? __builtin_nontemporal_load(dp) : dp[0];
+    const uint64_t a = NT ? __builtin_nontemporal_load(sp) : sp[0];
+    const uint64_t b = NT ? __builtin_nontemporal_load(sp + 1) : sp[1];
+    return MsMeta{(uint32_t)c, (int64_t)a, (uint32_t)b, (uint32_t)(b >> 32)};
+}
+
+// One finished run of a connection's datagrams into its entry: at most four 64-bit adds and the sticky flag.
+__device__ __forceinline__ void ms_run_add(cts_ms_conn_state* state, uint32_t conn, uint32_t n_conns, uint64_t bits,
+                                           uint32_t dg, uint32_t after, uint32_t err, uint32_t in)
+{
+    if (conn >= n_conns) return;  // a connection without an entry (and kNone, the key of lanes that count nowhere)
+    cts_ms_conn_state* e = state + conn;
+    if (bits) atomicAdd((unsigned long long*)&e->bits_received, (unsigned long long)bits);
+    if (err) atomicAdd((unsigned long long*)&e->error_frames, (unsigned long long)err);
+    if (dg) atomicAdd((unsigned long long*)&e->datagrams, (unsigned long long)dg);
+    if (after) atomicAdd((unsigned long long*)&e->datagrams_after_end, (unsigned long long)after);
+    if (in) e->received_any = 1u;
+}
+
+// The walk, the segmented scan and the LDS join are conn_accumulate's: every wave takes one contiguous span of the
+// batch, 64 datagrams per step; runs of equal conn_index are summed by shuffles, a run that reaches lane 63 is carried
+// into the wave's next tile, and the runs the workgroup's four waves leave open are joined in LDS. What is summed per
+// run: the bits (64-bit) and four counts, packed a byte each inside a tile (each at most 64): datagrams, datagrams
+// after the end, error frames, datagrams booked to the ring. Every datagram is judged against its connection's entry
+// as the last tick left it (finished, head) and against the final slot; the one datagram with g == F stores the
+// stream's error. Frame bytes go to the ring with one add per in-window datagram.
+template <bool NT>
+__global__ void __launch_bounds__(kBlock)
+    ms_conn_accumulate(const cts_buf_desc* __restrict__ descs, const cts_datagram_status* __restrict__ status,
+                       uint32_t n, uint32_t base_index, const uint32_t* __restrict__ conn_first_fail,
+                       cts_ms_conn_state* state, uint64_t* __restrict__ frame_bytes, uint64_t frame_elems,
+                       uint32_t n_conns, uint64_t* __restrict__ udp, uint32_t span)
+{
+    __shared__ uint64_t red[kBlock / 64][kCounterCount];
+    __shared__ uint64_t tail_sum[kBlock / 64][5];
+    __shared__ uint32_t tail_key[kBlock / 64][2];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t lo = ((uint64_t)blockIdx.x * (kBlock / 64) + threadIdx.x / 64) * span;
+    const uint64_t hi = lo + span < (uint64_t)n ? lo + span : (uint64_t)n;  // lo >= n: an empty span
+    uint64_t node_bits = 0;
+    uint32_t node_err = 0, node_dg = 0;  // per lane: fewer than 2^32 datagrams per launch
+    // the open run: the one that reached lane 63 of the previous tile (wave-uniform)
+    uint32_t ckey = kNone, cdg = 0, cafter = 0, cerr = 0, cin = 0;
+    uint64_t cbits = 0;
+    bool whole = true;  // the span so far is one run (wave-uniform)
+    // per-lane sums of the tiles that were nothing but the open run, not yet in cbits .. cin
+    uint64_t pbits = 0;
+    uint32_t pdg = 0, pafter = 0, perr = 0, pin = 0;
+    bool parked = false;
+    MsMeta mn = MsMeta{kNone, 0, 0u, 0u};
+    if (lo < hi) mn = ms_meta<NT>(descs, status, lo + lane < hi ? lo + lane : hi - 1);
+    for (uint64_t t = lo; t < hi; t += 64) {
+        const uint64_t i = t + lane;
+        const MsMeta m = mn;
+        if (t + 64 < hi) mn = ms_meta<NT>(descs, status, i + 64 < hi ? i + 64 : hi - 1);  // the next tile, early
+        const bool ok = i < hi;
+        const uint32_t key = ok ? m.conn : kNone;
+        const bool has = ok && m.conn < n_conns;  // a connection without a slot never fails and has no window
+        uint32_t first = kNone, fin = 0u, frames = 0u;
+        int64_t head = 0, final_frame = 0;
+        uint64_t fbase = 0;
+        if (has) {
+            const cts_ms_conn_state* e = state + m.conn;
+            first = conn_first_fail[m.conn];
+            fin = e->finished;
+            head = e->head_sequence_number;
+            final_frame = e->final_frame;
+            fbase = e->frame_base;
+            frames = e->frames;
+        }
+        const uint32_t kind = (m.fkp >> 16) & 0xFFu;
+        const bool clean = kind == CTS_DGRAM_DATA && (m.fkp >> 24) != 0u;
+        const uint32_t g = base_index + (uint32_t)i;  // base_index + n <= 0xFFFFFFFF (checked by the entry point)
+        uint64_t bits = 0;
+        uint32_t dg = 0, after = 0, err = 0, in = 0;
+        if (ok) {
+            if (has && (fin != 0u || g > first)) {
+                after = 1u;  // the renderer or a close ended the stream, or it failed on an earlier datagram
+            } else {
+                dg = 1u;
+                if (has && g == first) {
+                    // the datagram that fails the stream: UpdateLastError, once per connection
+                    cts_ms_conn_state* e = state + m.conn;
+                    e->last_error = kind == CTS_DGRAM_DATA ? CTS_STATUS_ERROR_DATA_DID_NOT_MATCH_BIT_PATTERN
+                                                           : CTS_STATUS_ERROR_NOT_ALL_DATA_TRANSFERRED;
+                    e->has_failure = 1u;
+                } else if (clean) {
+                    bits = (uint64_t)m.completed * 8u;
+                    if (has) {
+                        // FindSequenceNumber: sequence number s sits at (s - 1) mod frames of the connection's ring
+                        const bool inside = m.seq <= final_frame && m.seq >= head &&
+                                            (uint64_t)(m.seq - head) < (uint64_t)frames;
+                        const uint64_t at = inside ? fbase + (uint64_t)(m.seq - 1) % frames : frame_elems;
+                        if (at < frame_elems) {
+                            atomicAdd((unsigned long long*)&frame_bytes[at], (unsigned long long)m.completed);
+                            in = 1u;
+                        } else {
+                            err = 1u;
+                        }
+                    }
+                }
+            }
+        }
+        node_bits += bits;
+        node_err += err;
+        node_dg += dg;
+        // run heads, and for every lane the head of its run
+        const uint32_t below = (uint32_t)__shfl_up((int)key, 1, 64);
+        const bool rhead = lane == 0u || key != below;
+        const uint64_t heads = __ballot(rhead);
+        const uint32_t h = 63u - (uint32_t)__builtin_clzll(heads & (~0ull >> (63u - lane)));
+        const bool merge = (uint32_t)__shfl((int)key, 0, 64) == ckey;
+        if (heads == 1ull && merge) {
+            // the whole tile goes on the open run: per-lane sums, no shuffle (they join the run when it is next needed)
+            pbits += bits;
+            pdg += dg;
+            pafter += after;
+            perr += err;
+            pin += in;
+            parked = true;
+            continue;
+        }
+        if (parked) {
+            cbits += wave_sum64(pbits);
+            cdg += wave_sum(pdg);
+            cafter += wave_sum(pafter);
+            cerr += wave_sum(perr);
+            cin += wave_sum(pin);
+            pbits = 0;
+            pdg = pafter = perr = pin = 0;
+            parked = false;
+        }
+        // segmented inclusive scan: the bits, and the four counts a byte each (each <= 64)
+        uint64_t a = bits;
+        uint32_t c = dg | (after << 8) | (err << 16) | (in << 24);
+#pragma unroll
+        for (uint32_t off = 1; off < 64u; off <<= 1) {
+            const uint64_t ua = (uint64_t)__shfl_up((unsigned long long)a, off, 64);
+            const uint32_t uc = (uint32_t)__shfl_up((int)c, off, 64);
+            if (lane >= h + off) {
+                a += ua;
+                c += uc;
+            }
+        }
+        uint32_t rdg = c & 0xFFu, rafter = (c >> 8) & 0xFFu, rerr = (c >> 16) & 0xFFu, rin = c >> 24;
+        // the open run goes on in lane 0's run, or ends here
+        whole = whole && heads == 1ull && (merge || t == lo);
+        if (merge && h == 0u) {
+            a += cbits;
+            rdg += cdg;
+            rafter += cafter;
+            rerr += cerr;
+            rin += cin;
+        }
+        if (!merge && lane == 0u) ms_run_add(state, ckey, n_conns, cbits, cdg, cafter, cerr, cin);
+        const bool tail = lane == 63u || ((heads >> (lane + 1u)) & 1ull) != 0ull;
+        if (tail && lane != 63u) ms_run_add(state, key, n_conns, a, rdg, rafter, rerr, rin);
+        ckey = (uint32_t)__shfl((int)key, 63, 64);
+        cbits = (uint64_t)__shfl((unsigned long long)a, 63, 64);
+        cdg = (uint32_t)__shfl((int)rdg, 63, 64);
+        cafter = (uint32_t)__shfl((int)rafter, 63, 64);
+        cerr = (uint32_t)__shfl((int)rerr, 63, 64);
+        cin = (uint32_t)__shfl((int)rin, 63, 64);
+    }
+    if (parked) {
+        cbits += wave_sum64(pbits);
+        cdg += wave_sum(pdg);
+        cafter += wave_sum(pafter);
+        cerr += wave_sum(perr);
+        cin += wave_sum(pin);
+    }
+    // the waves' last open runs meet in LDS, as in conn_accumulate
+    if (lane == 0u) {
+        tail_sum[threadIdx.x / 64][0] = cbits;
+        tail_sum[threadIdx.x / 64][1] = cdg;
+        tail_sum[threadIdx.x / 64][2] = cafter;
+        tail_sum[threadIdx.x / 64][3] = cerr;
+        tail_sum[threadIdx.x / 64][4] = cin;
+        tail_key[threadIdx.x / 64][0] = ckey;
+        tail_key[threadIdx.x / 64][1] = whole ? 1u : 0u;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint32_t key = tail_key[0][0];
+        uint64_t acc[5] = {tail_sum[0][0], tail_sum[0][1], tail_sum[0][2], tail_sum[0][3], tail_sum[0][4]};
+        for (int w = 1; w < kBlock / 64; ++w) {
+            if (tail_key[w][1] == 0u || tail_key[w][0] != key) {
+                ms_run_add(state, key, n_conns, acc[0], (uint32_t)acc[1], (uint32_t)acc[2], (uint32_t)acc[3],
+                           (uint32_t)acc[4]);
+                key = tail_key[w][0];
+                acc[0] = acc[1] = acc[2] = acc[3] = acc[4] = 0;
+            }
+#pragma unroll
+            for (int k = 0; k < 5; ++k) acc[k] += tail_sum[w][k];
+        }
+        ms_run_add(state, key, n_conns, acc[0], (uint32_t)acc[1], (uint32_t)acc[2], (uint32_t)acc[3], (uint32_t)acc[4]);
+    }
+    uint64_t v[kCounterCount] = {0, 0, 0, 0, 0, 0};
+    v[kUdpBits] = wave_sum64(node_bits);
+    v[kUdpErrorFrames] = wave_sum(node_err);  // a wave's 64 lanes of one launch: still below 2^32
+    v[kUdpDatagrams] = wave_sum(node_dg);
+    block_add_six(v, red, udp);
+}
+
+// cts_media_stream_conns_render: one lane per listed connection, TimerCallback and RenderFrame
+// (ctsIOPatternMediaStream.cpp:360-530) on its entry; the frame outcomes go to the UDP block's shard.
+__global__ void __launch_bounds__(kBlock)
+    ms_conn_render(const uint32_t* __restrict__ ids, uint32_t n, cts_ms_conn_state* state,
+                   uint64_t* __restrict__ frame_bytes, uint32_t n_conns, uint64_t* __restrict__ udp,
+                   uint32_t* __restrict__ codes)
+{
+    __shared__ uint64_t red[kBlock / 64][kCounterCount];
+    uint32_t successful = 0, duplicate = 0;
+    uint64_t dropped = 0;  // a FatalAbort drops final_frame frames at once
+    const uint64_t step = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += step) {
+        const uint32_t c = ids[i];
+        uint32_t code = 0u;
+        if (c < n_conns) {
+            cts_ms_conn_state* e = state + c;
+            if (e->last_error != CTS_STATUS_IO_RUNNING || e->frames == 0u) {
+                code = e->finished;  // failed, ended or closed earlier: not rendered again
+            } else {
+                const uint32_t wheel = e->timer_wheel_offset + 1u;
+                e->timer_wheel_offset = wheel;
+                int64_t head = e->head_sequence_number;
+                const int64_t final_frame = e->final_frame;
+                if (wheel >= e->initial_buffer_frames && head <= final_frame) {
+                    if (e->received_any == 0u && head == 1) {
+                        // "have received nothing from the server": every frame counts as dropped, FatalAbort
+                        e->dropped_frames += (uint64_t)final_frame;
+                        dropped += (uint64_t)final_frame;
+                        e->finished = CTS_MS_CONN_FATAL;
+                        e->last_error = CTS_STATUS_ERROR_NOT_ALL_DATA_TRANSFERRED;
+                        code = 2u;
+                    } else {
+                        uint64_t* slot = frame_bytes + e->frame_base + (uint64_t)(head - 1) % e->frames;
+                        const uint64_t got = *slot;
+                        if (got == (uint64_t)e->frame_size_bytes) {
+                            e->successful_frames += 1u;
+                            successful += 1u;
+                        } else if (got < (uint64_t)e->frame_size_bytes) {
+                            e->dropped_frames += 1u;
+                            dropped += 1u;
+                        } else {
+                            e->duplicate_frames += 1u;
+                            duplicate += 1u;
+                        }
+                        *slot = 0;
+                        head += 1;
+                        e->head_sequence_number = head;
+                    }
+                }
+                if (code == 0u && head > final_frame) {
+                    e->finished = CTS_MS_CONN_FINISHED;
+                    e->last_error = 0u;
+                    code = 1u;
+                }
+            }
+        }
+        if (codes != nullptr) codes[i] = code;
+    }
+    uint64_t v[kCounterCount] = {0, 0, 0, 0, 0, 0};
+    v[kUdpSuccessful] = wave_sum(successful);  // fewer than 2^32 ids per launch
+    v[kUdpDropped] = wave_sum64(dropped);
+    v[kUdpDuplicate] = wave_sum(duplicate);
+    block_add_six(v, red, udp);
+}
+
+// cts_media_stream_conns_close: one wave per closed connection. Every lane reads the entry (one broadcast line), the
+// wave zeroes the connection's ring, lane 0 writes the result, empties the slot and leaves the entry ended; the class
+// counts and the byte sum go to the close block's shard by the route of conn_close.
+__global__ void __launch_bounds__(kBlock)
+    ms_conn_close(const uint32_t* __restrict__ ids, uint32_t n, uint32_t* __restrict__ conn_first_fail,
+                  cts_ms_conn_state* state, uint64_t* __restrict__ frame_bytes, uint32_t n_conns,
+                  cts_ms_conn_result* __restrict__ results, uint64_t* __restrict__ block)
+{
+    __shared__ uint64_t red[kBlock / 64][kCounterCount];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t step = (uint64_t)gridDim.x * (kBlock / 64);
+    uint32_t closed = 0, successful = 0, data_errors = 0, not_all = 0;  // wave-uniform
+    uint64_t bytes = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * (kBlock / 64) + threadIdx.x / 64; i < n; i += step) {
+        const uint32_t c = ids[i];
+        cts_ms_conn_result r = cts_ms_conn_result{0, 0, 0, 0, 0, 0, 0, 0, kNone, 0u, 0u, c, 0u, 0u};
+        if (c >= n_conns) {
+            r.flags = CTS_MS_CONN_RESULT_FLAG_BAD_CONN;
+        } else {
+            cts_ms_conn_state* e = state + c;
+            const cts_ms_conn_state s = *e;
+            uint32_t status = s.last_error;
+            if (status == CTS_STATUS_IO_RUNNING) {
+                // the device's own rule: a client closed while its renderer still runs did not get all its data
+                status = CTS_STATUS_ERROR_NOT_ALL_DATA_TRANSFERRED;
+                r.flags |= CTS_MS_CONN_RESULT_FLAG_RUNNING;
+            }
+            if (status == 0u) successful += 1u;
+            else if (status == CTS_STATUS_ERROR_DATA_DID_NOT_MATCH_BIT_PATTERN) data_errors += 1u;
+            else not_all += 1u;
+            closed += 1u;
+            bytes += s.bits_received / 8u;
+            r.bits_received = s.bits_received;
+            r.successful_frames = s.successful_frames;
+            r.dropped_frames = s.dropped_frames;
+            r.duplicate_frames = s.duplicate_frames;
+            r.error_frames = s.error_frames;
+            r.datagrams = s.datagrams;
+            r.datagrams_after_end = s.datagrams_after_end;
+            r.head_sequence_number = s.head_sequence_number;
+            if (s.has_failure != 0u) {
+                r.flags |= CTS_MS_CONN_RESULT_FLAG_HAS_FAILURE;
+                r.fail_datagram = (uint32_t)(s.datagrams - 1u);
+            }
+            r.first_fail = conn_first_fail[c];
+            r.status = status;
+            r.finished = s.finished;
+            for (uint64_t k = lane; k < (uint64_t)s.frames; k += 64) frame_bytes[s.frame_base + k] = 0;
+            if (lane == 0u) {
+                // late datagrams count as after the end until a fresh entry is written over this one
+                conn_first_fail[c] = kNone;
+                e->last_error = status;
+                e->finished = s.finished != 0u ? s.finished : CTS_MS_CONN_CLOSED;
+            }
+        }
+        if (results != nullptr && lane == 0u) results[i] = r;
+    }
+    uint64_t v[kCounterCount] = {0, 0, 0, 0, 0, 0};
+    v[kCloseClosed] = closed;
+    v[kCloseSuccessful] = successful;
+    v[kCloseDataErrors] = data_errors;
+    v[kCloseNotAllData] = not_all;
+    v[kCloseBytesRecv] = bytes;
+    block_add_six(v, red, block);
+}
+
+// ---------------------------------------------------------------------------------------------
 // fill: the write-bound twin. Interior chunks are 16-byte stores; the (at most
 // two) edge chunks of a span write only their own bytes, so neighbouring buffers
 // sharing a 16-byte line are never touched.
@@ -1825,13 +2188,24 @@ struct MsFrames {
 
 // The header chunks and the payload's edge chunks are loaded ahead of the rounds with the default (L2-allocating)
 // policy, as verify_quad_kernel's edges (nontemporal, their lines were often gone from L2 when the rounds asked again).
-template <bool NT, bool STRIDED, int RING, bool STATUS = false, bool FRAMES = false>
-__global__ void __launch_bounds__(kBlock)
-    media_stream_verify_quad_kernel(const uint8_t* __restrict__ arena, uint64_t arena_bytes, MsSource src, uint32_t n,
-                                    void* __restrict__ records, cts_verify_result* __restrict__ results,
-                                    uint64_t* __restrict__ counters, uint32_t per, MsFrames fr = MsFrames{})
+// ORD (cts_media_stream_verify_status_at): the first-failure slots of the device-resident connections. The leader of
+// a team whose datagram is an exception (it fails the stream: anything but clean DATA and ID) reads the descriptor's
+// conn_index and lowers the connection's slot to the datagram's stream ordinal; the common path gains no load.
+struct MsOrdinals {
+    uint32_t* conn_first_fail;
+    uint32_t n_conns;
+    uint32_t base_index;  // ordinal of datagram 0; base_index + n <= 0xFFFFFFFF (checked by the entry point)
+};
+
+template <bool NT, bool STRIDED, int RING, bool STATUS, bool FRAMES, bool ORD>
+__device__ __forceinline__ void ms_verify_quad_body(const uint8_t* __restrict__ arena, uint64_t arena_bytes,
+                                                    MsSource src, uint32_t n, void* __restrict__ records,
+                                                    cts_verify_result* __restrict__ results,
+                                                    uint64_t* __restrict__ counters, uint32_t per, MsFrames fr,
+                                                    MsOrdinals ord)
 {
     static_assert(RING > 0 || FRAMES, "per-datagram outputs go through the per-wave ring");
+    static_assert(!ORD || (STATUS && !STRIDED), "ordinals: the status form over descriptors");
     constexpr int U = kQuadLoads;
     constexpr int TEAMS = kBlock / kQuadTeam;
     __shared__ uint64_t s_fbytes[FRAMES ? kFramesLds : 1];  // FRAMES: this workgroup's bytes per window slot
@@ -1945,6 +2319,12 @@ __global__ void __launch_bounds__(kBlock)
             if (lane == 0u && live) {
                 auto& o_ = qring[team >> 2].slot[rs];
                 CTS_MS_STAGE(o_);
+                if constexpr (ORD) {
+                    if (data ? first != kNone : kind != CTS_DGRAM_ID) {  // rare: the datagram fails its stream
+                        const uint32_t conn = src.descs[i].conn_index;
+                        if (conn < ord.n_conns) atomicMin(&ord.conn_first_fail[conn], ord.base_index + i);
+                    }
+                }
             }
             auto& g = qring[team >> 2];
             const uint32_t i0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)i);
@@ -1981,6 +2361,28 @@ __global__ void __launch_bounds__(kBlock)
             atomicAdd((unsigned long long*)&sh[threadIdx.x], (unsigned long long)s_ftot[threadIdx.x]);
     }
     qc.flush<TEAMS>(ctr, team, lane, counters);
+}
+
+// The receive pass of cts_media_stream_verify / _status / _frames and their strided forms. Its name and arguments are
+// what tests/test_abi.py and the profiling tools look the MediaStream kernels up by, so they stay as they are.
+template <bool NT, bool STRIDED, int RING, bool STATUS = false, bool FRAMES = false>
+__global__ void __launch_bounds__(kBlock)
+    media_stream_verify_quad_kernel(const uint8_t* __restrict__ arena, uint64_t arena_bytes, MsSource src, uint32_t n,
+                                    void* __restrict__ records, cts_verify_result* __restrict__ results,
+                                    uint64_t* __restrict__ counters, uint32_t per, MsFrames fr = MsFrames{})
+{
+    ms_verify_quad_body<NT, STRIDED, RING, STATUS, FRAMES, false>(arena, arena_bytes, src, n, records, results,
+                                                                  counters, per, fr, MsOrdinals{nullptr, 0u, 0u});
+}
+
+// cts_media_stream_verify_status_at: the status form over descriptors, the same body, with the slot claim.
+template <bool NT>
+__global__ void __launch_bounds__(kBlock)
+    ms_verify_status_ordinal(const uint8_t* __restrict__ arena, uint64_t arena_bytes, MsSource src, uint32_t n,
+                             void* __restrict__ status, uint64_t* __restrict__ counters, uint32_t per, MsOrdinals ord)
+{
+    ms_verify_quad_body<NT, false, 64, true, false, true>(arena, arena_bytes, src, n, status, nullptr, counters, per,
+                                                          MsFrames{}, ord);
 }
 
 // Send: header {u16 0, i64 seq, i64 qpc, i64 qpf} + P[0 .. length-26) per datagram
@@ -2676,6 +3078,50 @@ hipError_t launch_conn_slots_rebase(uint32_t* conn_first_fail, uint32_t n_conns,
     return hipGetLastError();
 }
 
+// cts_media_stream_conns_accumulate: conn_accumulate's grid and spans
+hipError_t launch_ms_conn_accumulate(const cts_buf_desc* descs, const cts_datagram_status* status, uint32_t n,
+                                     uint32_t base_index, const uint32_t* conn_first_fail, cts_ms_conn_state* conns,
+                                     uint64_t* frame_bytes, uint64_t frame_elems, uint32_t n_conns,
+                                     uint64_t* udp_counters, hipStream_t stream, const LaunchGeometry& geo)
+{
+    if (n == 0) return hipSuccess;
+    const uint32_t grid = lane_per_item_grid(n, geo);
+    const uint64_t waves = (uint64_t)grid * (kBlock / 64);
+    const uint32_t span = (uint32_t)((((uint64_t)n + waves - 1) / waves + 63u) / 64u * 64u);
+    if (geo.nontemporal)
+        ms_conn_accumulate<true><<<grid, kBlock, 0, stream>>>(descs, status, n, base_index, conn_first_fail, conns,
+                                                              frame_bytes, frame_elems, n_conns, udp_counters, span);
+    else
+        ms_conn_accumulate<false><<<grid, kBlock, 0, stream>>>(descs, status, n, base_index, conn_first_fail, conns,
+                                                               frame_bytes, frame_elems, n_conns, udp_counters, span);
+    return hipGetLastError();
+}
+
+hipError_t launch_ms_conn_render(const uint32_t* conn_ids, uint32_t n, cts_ms_conn_state* conns, uint64_t* frame_bytes,
+                                 uint32_t n_conns, uint64_t* udp_counters, uint32_t* codes, hipStream_t stream,
+                                 const LaunchGeometry& geo)
+{
+    if (n == 0) return hipSuccess;
+    ms_conn_render<<<lane_per_item_grid(n, geo), kBlock, 0, stream>>>(conn_ids, n, conns, frame_bytes, n_conns,
+                                                                      udp_counters, codes);
+    return hipGetLastError();
+}
+
+// one wave per id, grid-stride beyond refview's grid cap
+hipError_t launch_ms_conn_close(const uint32_t* conn_ids, uint32_t n, uint32_t* conn_first_fail,
+                                cts_ms_conn_state* conns, uint64_t* frame_bytes, uint32_t n_conns,
+                                cts_ms_conn_result* results, uint64_t* close_counters, hipStream_t stream,
+                                const LaunchGeometry& geo)
+{
+    if (n == 0) return hipSuccess;
+    const uint64_t want = ((uint64_t)n + kBlock / 64 - 1) / (kBlock / 64);
+    const uint64_t cap = (uint64_t)(geo.num_cus > 0 ? geo.num_cus : 1) * kRefviewBlocksPerCu;
+    ms_conn_close<<<(uint32_t)(want < cap ? want : cap), kBlock, 0, stream>>>(conn_ids, n, conn_first_fail, conns,
+                                                                             frame_bytes, n_conns, results,
+                                                                             close_counters);
+    return hipGetLastError();
+}
+
 // grid of the batched datagram fills: whole batches per workgroup, at most ring_fill_blocks_per_cu per CU
 static inline uint32_t batched_fill_grid(uint32_t n, const LaunchGeometry& geo)
 {
@@ -2773,6 +3219,25 @@ hipError_t launch_media_stream_status(const uint8_t* arena, uint64_t arena_bytes
         else CTS_MS_STATUS(false, false);
     }
 #undef CTS_MS_STATUS
+    return hipGetLastError();
+}
+
+// cts_media_stream_verify_status_at: launch_media_stream_status's walk over descriptors, with the slot claim
+hipError_t launch_media_stream_status_at(const uint8_t* arena, uint64_t arena_bytes, const cts_buf_desc* descs,
+                                        uint32_t n, uint32_t base_index, cts_datagram_status* status,
+                                        uint64_t* counters, uint32_t* conn_first_fail, uint32_t n_conns,
+                                        hipStream_t stream, const LaunchGeometry& geo)
+{
+    if (n == 0) return hipSuccess;
+    const ContigGrid cg = contig_grid(n, geo);
+    const MsSource src{descs, nullptr, 0u};
+    const MsOrdinals ord{conn_first_fail, n_conns, base_index};
+    if (geo.nontemporal)
+        ms_verify_status_ordinal<true><<<cg.grid, kBlock, 0, stream>>>(arena, arena_bytes, src, n, status, counters,
+                                                                       cg.per, ord);
+    else
+        ms_verify_status_ordinal<false><<<cg.grid, kBlock, 0, stream>>>(arena, arena_bytes, src, n, status, counters,
+                                                                        cg.per, ord);
     return hipGetLastError();
 }
 

@@ -12,8 +12,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (CtsAllreduceSetup, CtsCounters, CtsCountersClose, CtsCountersEx, CtsCountersRef, CtsVerifyResult,
-                   check, lib)
+from ._lib import (CtsAllreduceSetup, CtsCounters, CtsCountersClose, CtsCountersEx, CtsCountersRef, CtsCountersUdp,
+                   CtsVerifyResult, check, lib)
 from .types import CONN_RESULT_DTYPE, CONN_STATE_DTYPE, DESC_DTYPE, RESULT_DTYPE
 
 try:
@@ -154,6 +154,23 @@ def counters_allreduce_close(engines: Sequence["Engine"], blocks, streams=None) 
     E, C, S, n = _multi_args(engines, blocks, streams)
     out = CtsCountersClose()
     check("cts_counters_allreduce_close", lib().cts_counters_allreduce_close(E, C, S, n, ctypes.byref(out)))
+    return out.as_dict()
+
+
+def counters_read_multi_udp(engines: Sequence["Engine"], blocks, streams=None) -> dict:
+    """cts_counters_read_multi_udp: the node-wide UdpStatusDetails (the MediaStream connections' UDP blocks), folded
+    on the host."""
+    E, C, S, n = _multi_args(engines, blocks, streams)
+    out = CtsCountersUdp()
+    check("cts_counters_read_multi_udp", lib().cts_counters_read_multi_udp(E, C, S, n, ctypes.byref(out)))
+    return out.as_dict()
+
+
+def counters_allreduce_udp(engines: Sequence["Engine"], blocks, streams=None) -> dict:
+    """cts_counters_allreduce_udp: the node-wide UdpStatusDetails reduced on the GPUs (the same u64 x 6 over RCCL)."""
+    E, C, S, n = _multi_args(engines, blocks, streams)
+    out = CtsCountersUdp()
+    check("cts_counters_allreduce_udp", lib().cts_counters_allreduce_udp(E, C, S, n, ctypes.byref(out)))
     return out.as_dict()
 
 
@@ -405,6 +422,13 @@ class Engine:
         c = CtsCountersClose()
         check("cts_counters_read_close", self._L.cts_counters_read_close(self._h, _ptr(close_counters),
                                                                        ctypes.byref(c), _stream(stream)))
+        return c.as_dict()
+
+    def read_counters_udp(self, udp_counters, stream=None) -> dict:
+        """cts_counters_read_udp: a UDP block (media_stream.ConnectionTable) folded, as cts_counters_udp."""
+        c = CtsCountersUdp()
+        check("cts_counters_read_udp", self._L.cts_counters_read_udp(self._h, _ptr(udp_counters), ctypes.byref(c),
+                                                                   _stream(stream)))
         return c.as_dict()
 
     def new_results(self, n: int):

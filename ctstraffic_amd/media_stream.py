@@ -372,3 +372,121 @@ class MediaStreamClient:
 
     def connection_id(self) -> str:
         return lib().cts_media_stream_client_connection_id(self._h).decode()
+
+
+# ---- MediaStream connections on the device-resident path (include/cts_media_stream_conns.h) ---------------------
+def conn_init(frame_size_bytes: int, buffered_frames: int, stream_length_frames: int, frame_base: int = 0,
+              datagram_max_size: int = 1400, frames_per_second: int = 60) -> np.ndarray:
+    """cts_ms_conn_init: a fresh cts_ms_conn_state (one MS_CONN_STATE_DTYPE record) for a client with these settings,
+    its ring at frame_base. Raises CtsError where cts_media_stream_client_create would refuse the settings."""
+    from .types import MS_CONN_STATE_DTYPE
+
+    s = Settings(frame_size_bytes, datagram_max_size, frames_per_second, buffered_frames, stream_length_frames)
+    out = np.zeros(1, dtype=MS_CONN_STATE_DTYPE)
+    check("cts_ms_conn_init", lib().cts_ms_conn_init(ctypes.addressof(s), frame_base, out.ctypes.data))
+    return out[0]
+
+
+class ConnectionTable:
+    """Many MediaStream clients on one device: the entry table, the rings, the first-failure slots and the UDP block,
+    with the per-batch passes, the render tick and the close as methods.
+
+    settings: (frame_size_bytes, buffered_frames, stream_length_frames) per connection slot. Per batch call
+    :meth:`verify` then :meth:`accumulate` with the batch's base_index (its first stream ordinal), :meth:`render` at a
+    tick, :meth:`close` to report and recycle slots, :meth:`reinit` before a slot's next connection."""
+
+    def __init__(self, engine, settings, device=None):
+        import torch
+
+        from .types import MS_CONN_STATE_DTYPE
+
+        self.engine = engine
+        self.device = device or "cuda:%d" % engine.device
+        self.fresh = np.zeros(len(settings), dtype=MS_CONN_STATE_DTYPE)
+        base = 0
+        for c, (frame_size, buffered, length) in enumerate(settings):
+            self.fresh[c] = conn_init(frame_size, buffered, length, frame_base=base)
+            base += int(self.fresh[c]["frames"])
+        self.n_conns, self.frame_elems = len(settings), base
+        self.conns = torch.from_numpy(self.fresh.view(np.int64).copy()).to(self.device)
+        self.frame_bytes = torch.zeros(max(1, base), dtype=torch.int64, device=self.device)
+        self.slots = torch.full((max(1, self.n_conns),), -1, dtype=torch.int32, device=self.device)[: self.n_conns]
+        self.udp = engine.new_counters()
+
+    def verify(self, arena, descs, base_index: int = 0, status=None, counters=None, stream=None) -> None:
+        """cts_media_stream_verify_status_at: the receive pass; lowers the slots of connections with an exception."""
+        from .engine import _check_outputs, _nbytes, _stream
+
+        n = _nbytes(descs) // DESC_DTYPE.itemsize
+        _check_outputs(n, None, counters)
+        _check_status(n, status)
+        check("cts_media_stream_verify_status_at",
+              self.engine._L.cts_media_stream_verify_status_at(
+                  self.engine._h, _ptr(arena), _nbytes(arena), _ptr(descs), n, base_index, _ptr(status),
+                  _ptr(counters), _ptr(self.slots), self.n_conns, _stream(stream)))
+
+    def accumulate(self, arena_bytes: int, descs, status, base_index: int = 0, stream=None) -> None:
+        """cts_media_stream_conns_accumulate: the accounting pass over the batch's descriptors and statuses."""
+        from .engine import _nbytes, _stream
+
+        n = _nbytes(descs) // DESC_DTYPE.itemsize
+        if status is None:
+            raise ValueError("the accounting pass reads the batch's statuses")
+        _check_status(n, status)
+        check("cts_media_stream_conns_accumulate",
+              self.engine._L.cts_media_stream_conns_accumulate(
+                  self.engine._h, arena_bytes, _ptr(descs), _ptr(status), n, base_index, _ptr(self.slots),
+                  _ptr(self.conns), _ptr(self.frame_bytes), self.frame_elems, self.n_conns, _ptr(self.udp),
+                  _stream(stream)))
+
+    def render(self, conn_ids, codes=None, stream=None) -> None:
+        """cts_media_stream_conns_render: one tick of conn_ids (uint32/int32 device tensor, distinct); codes: None or
+        an int32 device tensor of as many elements."""
+        from .engine import _nbytes, _stream
+
+        n = _nbytes(conn_ids) // 4
+        if codes is not None and _nbytes(codes) < 4 * n:
+            raise ValueError("codes holds %d bytes, %d ids need %d" % (_nbytes(codes), n, 4 * n))
+        check("cts_media_stream_conns_render",
+              self.engine._L.cts_media_stream_conns_render(self.engine._h, _ptr(conn_ids), n, _ptr(self.conns),
+                                                           _ptr(self.frame_bytes), self.n_conns, _ptr(self.udp),
+                                                           _ptr(codes), _stream(stream)))
+
+    def close(self, conn_ids, close_counters, results=None, stream=None) -> None:
+        """cts_media_stream_conns_close: results None or 88 bytes per id (MS_CONN_RESULT_DTYPE)."""
+        from .engine import _check_outputs, _nbytes, _stream
+        from .types import MS_CONN_RESULT_DTYPE
+
+        n = _nbytes(conn_ids) // 4
+        _check_outputs(0, None, close_counters)
+        if results is not None and _nbytes(results) < n * MS_CONN_RESULT_DTYPE.itemsize:
+            raise ValueError("results holds %d bytes, %d ids need %d" % (_nbytes(results), n,
+                                                                         n * MS_CONN_RESULT_DTYPE.itemsize))
+        check("cts_media_stream_conns_close",
+              self.engine._L.cts_media_stream_conns_close(self.engine._h, _ptr(conn_ids), n, _ptr(self.slots),
+                                                          _ptr(self.conns), _ptr(self.frame_bytes), self.n_conns,
+                                                          _ptr(results), _ptr(close_counters), _stream(stream)))
+
+    def new_results(self, n: int):
+        import torch
+
+        from .types import MS_CONN_RESULT_DTYPE
+
+        return torch.zeros(n * (MS_CONN_RESULT_DTYPE.itemsize // 8), dtype=torch.int64, device=self.device)
+
+    def reinit(self, conn_ids) -> None:
+        """Fresh entries over the listed slots (host ids): the slots' next connections, same settings."""
+        import torch
+
+        words = self.fresh.dtype.itemsize // 8
+        view = self.conns.view(-1, words)
+        ids = torch.as_tensor(list(conn_ids), dtype=torch.int64, device=self.device)
+        view[ids] = torch.from_numpy(self.fresh.view(np.int64).reshape(-1, words).copy()).to(self.device)[ids]
+
+    def read(self):
+        """(entries MS_CONN_STATE_DTYPE, ring uint64, slots uint32) copied to the host."""
+        return (self.conns.cpu().numpy().view(self.fresh.dtype), self.frame_bytes.cpu().numpy().view(np.uint64)
+                [: self.frame_elems], self.slots.cpu().numpy().view(np.uint32))
+
+    def read_udp(self, stream=None) -> dict:
+        return self.engine.read_counters_udp(self.udp, stream=stream)

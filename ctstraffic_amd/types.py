@@ -81,3 +81,50 @@ CONN_RESULT_FLAG_BAD_CONN = 0x1
 # cts_counters_close: the six words of a close block
 CLOSE_FIELDS = ("connections_closed", "successful", "data_errors", "not_all_data", "too_much_data", "bytes_recv")
 assert CONN_STATE_DTYPE.itemsize == 32 and CONN_RESULT_DTYPE.itemsize == 48
+# cts_ms_conn_state (include/cts_media_stream_conns.h): one MediaStream connection's device entry
+MS_CONN_STATE_DTYPE = np.dtype(
+    [
+        ("bits_received", "<u8"),
+        ("successful_frames", "<u8"),
+        ("dropped_frames", "<u8"),
+        ("duplicate_frames", "<u8"),
+        ("error_frames", "<u8"),
+        ("datagrams", "<u8"),
+        ("datagrams_after_end", "<u8"),
+        ("head_sequence_number", "<i8"),
+        ("final_frame", "<i8"),
+        ("frame_base", "<u8"),
+        ("frames", "<u4"),
+        ("frame_size_bytes", "<u4"),
+        ("initial_buffer_frames", "<u4"),
+        ("timer_wheel_offset", "<u4"),
+        ("last_error", "<u4"),
+        ("finished", "<u4"),
+        ("received_any", "<u4"),
+        ("has_failure", "<u4"),
+    ]
+)
+# cts_ms_conn_result: what cts_media_stream_conns_close reports for one connection
+MS_CONN_RESULT_DTYPE = np.dtype(
+    [
+        ("bits_received", "<u8"),
+        ("successful_frames", "<u8"),
+        ("dropped_frames", "<u8"),
+        ("duplicate_frames", "<u8"),
+        ("error_frames", "<u8"),
+        ("datagrams", "<u8"),
+        ("datagrams_after_end", "<u8"),
+        ("head_sequence_number", "<i8"),
+        ("fail_datagram", "<u4"),
+        ("first_fail", "<u4"),
+        ("status", "<u4"),
+        ("conn_index", "<u4"),
+        ("flags", "<u4"),
+        ("finished", "<u4"),
+    ]
+)
+MS_CONN_RESULT_FLAG_BAD_CONN, MS_CONN_RESULT_FLAG_HAS_FAILURE, MS_CONN_RESULT_FLAG_RUNNING = 0x1, 0x2, 0x4
+MS_CONN_RUNNING, MS_CONN_FINISHED, MS_CONN_FATAL, MS_CONN_CLOSED = 0, 1, 2, 3
+# cts_counters_udp: the six words of a UDP block
+UDP_FIELDS = ("bits_received", "successful_frames", "dropped_frames", "duplicate_frames", "error_frames", "datagrams")
+assert MS_CONN_STATE_DTYPE.itemsize == 112 and MS_CONN_RESULT_DTYPE.itemsize == 88

@@ -385,3 +385,351 @@ def materialize(engine, w: Workload, device: str = "cuda", fill_stream=None):
         xor = torch.from_numpy(w.corrupt_xor).to(device)
         arena[pos] = arena[pos] ^ xor
     return arena, descs
+
+
+# ---- MediaStream connections on the device-resident path (include/cts_media_stream_conns.h) -------------------
+UDP_FIELDS = ("bits_received", "successful_frames", "dropped_frames", "duplicate_frames", "error_frames", "datagrams")
+STATUS_IO_RUNNING = 2147483647  # c_statusIoRunning, ctsIOPattern.h:46
+DGRAM_DATA, DGRAM_ID, DGRAM_ZERO, DGRAM_SHORT, DGRAM_UNKNOWN, DGRAM_BAD_DESC = range(6)
+
+
+def media_stream_conn_entries(settings):
+    """cts_ms_conn_init as a model, for a list of (frame_size_bytes, buffered_frames, stream_length_frames): fresh
+    entries with their rings laid out one after the other. Returns (MS_CONN_STATE_DTYPE[len(settings)], frame_elems).
+    Raises ValueError where cts_ms_conn_init returns CTS_E_INVALID."""
+    from .types import MS_CONN_STATE_DTYPE
+
+    e = np.zeros(len(settings), dtype=MS_CONN_STATE_DTYPE)
+    base = 0
+    for c, (frame_size, buffered, length) in enumerate(settings):
+        if frame_size <= 0 or length <= 0 or length > 0xFFFFFFFF:
+            raise ValueError("connection %d: frame size %d, stream length %d" % (c, frame_size, length))
+        initial = min(length, buffered)
+        if 2 * initial < 2 or 2 * initial > 0xFFFFFFFF:
+            raise ValueError("connection %d: a queue of %d frames" % (c, 2 * initial))
+        e[c]["head_sequence_number"] = 1
+        e[c]["final_frame"] = length
+        e[c]["frame_base"] = base
+        e[c]["frames"] = 2 * initial
+        e[c]["frame_size_bytes"] = frame_size
+        e[c]["initial_buffer_frames"] = initial
+        e[c]["timer_wheel_offset"] = initial
+        e[c]["last_error"] = STATUS_IO_RUNNING
+        base += 2 * initial
+    return e, base
+
+
+def datagram_exceptions(kind, passed) -> np.ndarray:
+    """The datagrams that fail their stream: anything but an ID datagram and a DATA datagram whose payload verified."""
+    kind = np.asarray(kind)
+    return np.where(kind == DGRAM_DATA, ~np.asarray(passed, dtype=bool), kind != DGRAM_ID)
+
+
+class MediaStreamConnectionView:
+    """The device-resident MediaStream connections as a model: what cts_media_stream_verify_status_at does to the
+    slots, and cts_media_stream_conns_accumulate, _render and _close to the entries, the rings, the UDP block and
+    the close block. One jitter window per connection; a datagram's stream ordinal is base_index + its index."""
+
+    def __init__(self, entries: np.ndarray, frame_elems: int, slots=None):
+        from .types import MS_CONN_STATE_DTYPE
+
+        self.entries = np.array(entries, dtype=MS_CONN_STATE_DTYPE, copy=True)
+        self.n_conns = len(self.entries)
+        self.ring = np.zeros(frame_elems, dtype=np.uint64)
+        self.slots = (np.full(self.n_conns, EMPTY_SLOT, dtype=np.uint32) if slots is None
+                      else np.array(slots, dtype=np.uint32, copy=True))
+        self.udp = dict.fromkeys(UDP_FIELDS, 0)
+        self.close_block = dict.fromkeys(CLOSE_FIELDS, 0)
+
+    def receive(self, conn_index, kind, passed, base_index: int = 0) -> None:
+        """The receive pass's slot claims: the lowest exception ordinal per connection with a slot."""
+        conn = np.asarray(conn_index, dtype=np.int64)
+        pick = datagram_exceptions(kind, passed) & (conn < self.n_conns)
+        g = (base_index + np.arange(len(conn), dtype=np.int64)).astype(np.uint32)
+        np.minimum.at(self.slots, conn[pick], g[pick])
+
+    def accumulate(self, conn_index, status, base_index: int = 0) -> None:
+        """The accounting pass over one batch: conn_index[i] and status[i] (DGRAM_STATUS_DTYPE) of datagram i. Every
+        datagram is judged against its entry as the last tick left it and against the final slot."""
+        e, conn = self.entries, np.asarray(conn_index, dtype=np.int64)
+        for i in range(len(conn)):
+            c, g = int(conn[i]), base_index + i
+            kind, completed = int(status["kind"][i]), int(status["completed_bytes"][i])
+            clean = kind == DGRAM_DATA and bool(status["pass"][i])
+            if c >= self.n_conns:
+                self.udp["datagrams"] += 1
+                if clean:
+                    self.udp["bits_received"] += 8 * completed
+                continue
+            first = int(self.slots[c])
+            if e["finished"][c] != 0 or g > first:
+                e["datagrams_after_end"][c] += 1
+                continue
+            e["datagrams"][c] += 1
+            self.udp["datagrams"] += 1
+            if g == first:
+                e["last_error"][c] = (STATUS_ERROR_DATA_DID_NOT_MATCH_BIT_PATTERN if kind == DGRAM_DATA
+                                      else STATUS_ERROR_NOT_ALL_DATA_TRANSFERRED)
+                e["has_failure"][c] = 1
+            elif clean:
+                e["bits_received"][c] += 8 * completed
+                self.udp["bits_received"] += 8 * completed
+                seq, head, frames = int(status["sequence_number"][i]), int(e["head_sequence_number"][c]), int(e["frames"][c])
+                at = int(e["frame_base"][c]) + (seq - 1) % frames if frames else len(self.ring)
+                if seq > int(e["final_frame"][c]) or seq < head or seq > head + frames - 1 or at >= len(self.ring):
+                    e["error_frames"][c] += 1
+                    self.udp["error_frames"] += 1
+                else:
+                    self.ring[at] += completed
+                    e["received_any"][c] = 1
+
+    def render(self, conn_ids) -> np.ndarray:
+        """One render tick of the listed connections. Returns the codes: 0 keep, 1 finished, 2 fatal; a connection
+        that is not rendered reports its entry's finished, an id without an entry 0."""
+        e, codes = self.entries, np.zeros(len(conn_ids), dtype=np.uint32)
+        for i, c in enumerate(int(x) for x in conn_ids):
+            if c >= self.n_conns:
+                continue
+            if e["last_error"][c] != STATUS_IO_RUNNING or e["frames"][c] == 0:
+                codes[i] = e["finished"][c]
+                continue
+            e["timer_wheel_offset"][c] += 1
+            head, final = int(e["head_sequence_number"][c]), int(e["final_frame"][c])
+            if e["timer_wheel_offset"][c] >= e["initial_buffer_frames"][c] and head <= final:
+                if e["received_any"][c] == 0 and head == 1:
+                    e["dropped_frames"][c] += final
+                    self.udp["dropped_frames"] += final
+                    e["finished"][c] = 2
+                    e["last_error"][c] = STATUS_ERROR_NOT_ALL_DATA_TRANSFERRED
+                    codes[i] = 2
+                    continue
+                at = int(e["frame_base"][c]) + (head - 1) % int(e["frames"][c])
+                got, want = int(self.ring[at]), int(e["frame_size_bytes"][c])
+                f = "successful_frames" if got == want else "dropped_frames" if got < want else "duplicate_frames"
+                e[f][c] += 1
+                self.udp[f] += 1
+                self.ring[at] = 0
+                head += 1
+                e["head_sequence_number"][c] = head
+            if head > final:
+                e["finished"][c] = 1
+                e["last_error"][c] = 0
+                codes[i] = 1
+        return codes
+
+    def close(self, conn_ids) -> np.ndarray:
+        """Close the distinct connections conn_ids. Returns MS_CONN_RESULT_DTYPE[len(conn_ids)]."""
+        from .types import (MS_CONN_CLOSED, MS_CONN_RESULT_DTYPE, MS_CONN_RESULT_FLAG_BAD_CONN,
+                            MS_CONN_RESULT_FLAG_HAS_FAILURE, MS_CONN_RESULT_FLAG_RUNNING)
+
+        e, res = self.entries, np.zeros(len(conn_ids), dtype=MS_CONN_RESULT_DTYPE)
+        assert len(set(int(x) for x in conn_ids)) == len(conn_ids)
+        for i, c in enumerate(int(x) for x in conn_ids):
+            r = res[i]
+            r["conn_index"], r["fail_datagram"] = c, EMPTY_SLOT
+            if c >= self.n_conns:
+                r["flags"] = MS_CONN_RESULT_FLAG_BAD_CONN
+                continue
+            status, flags = int(e["last_error"][c]), 0
+            if status == STATUS_IO_RUNNING:
+                status, flags = STATUS_ERROR_NOT_ALL_DATA_TRANSFERRED, MS_CONN_RESULT_FLAG_RUNNING
+            for f in ("bits_received", "successful_frames", "dropped_frames", "duplicate_frames", "error_frames",
+                      "datagrams", "datagrams_after_end", "head_sequence_number", "finished"):
+                r[f] = e[f][c]
+            if e["has_failure"][c]:
+                flags |= MS_CONN_RESULT_FLAG_HAS_FAILURE
+                r["fail_datagram"] = int(e["datagrams"][c]) - 1
+            r["first_fail"], r["status"], r["flags"] = self.slots[c], status, flags
+            cls = ("successful" if status == 0 else
+                   "data_errors" if status == STATUS_ERROR_DATA_DID_NOT_MATCH_BIT_PATTERN else "not_all_data")
+            self.close_block["connections_closed"] += 1
+            self.close_block[cls] += 1
+            self.close_block["bytes_recv"] += int(e["bits_received"][c]) // 8
+            self.slots[c] = EMPTY_SLOT
+            b = int(e["frame_base"][c])
+            self.ring[b:b + int(e["frames"][c])] = 0
+            e["last_error"][c] = status
+            if e["finished"][c] == 0:
+                e["finished"][c] = MS_CONN_CLOSED
+        return res
+
+    def rebase(self, delta: int) -> None:
+        self.slots = rebase_slots(self.slots, delta)
+
+    def reinit(self, conn_ids, fresh: np.ndarray) -> None:
+        """Fresh entries written over the listed ones (the caller's copy to the device)."""
+        for c in conn_ids:
+            self.entries[int(c)] = fresh[int(c)]
+
+
+def media_stream_connection_view(entries: np.ndarray, frame_elems: int, slots=None) -> MediaStreamConnectionView:
+    """A model of the device-resident MediaStream connections over `entries` (media_stream_conn_entries) and a ring
+    array of frame_elems elements; see MediaStreamConnectionView."""
+    return MediaStreamConnectionView(entries, frame_elems, slots)
+
+
+_PATTERN_PREFIX = None
+
+
+def _pattern_prefix(n: int) -> np.ndarray:
+    """P[0 .. n): the bytes a MediaStream payload carries (every datagram starts at pattern offset 0)."""
+    global _PATTERN_PREFIX
+    if _PATTERN_PREFIX is None or len(_PATTERN_PREFIX) < n:
+        from ._lib import lib
+
+        L = lib()
+        _PATTERN_PREFIX = np.array([L.cts_pattern_byte(i) for i in range(max(n, 2048))], dtype=np.uint8)
+    return _PATTERN_PREFIX[:n]
+
+
+@dataclass
+class MsConnBatch:
+    descs: np.ndarray   # DESC_DTYPE, conn_index = the connection
+    arena: np.ndarray   # uint8: the datagrams as received
+    base_index: int     # stream ordinal of datagram 0
+    ticks: int          # render ticks after the batch
+
+
+@dataclass
+class MsConnPlan:
+    settings: list      # (frame_size_bytes, buffered_frames, stream_length_frames) per connection
+    roles: list         # what each connection's traffic is made to do
+    batches: list       # MsConnBatch
+    max_datagram: int
+
+    @property
+    def n_conns(self) -> int:
+        return len(self.settings)
+
+
+MS_CONN_ROLES = ("mismatch_first", "success", "duplicate", "dropped", "stale_future", "id_success", "short_unknown",
+                 "unknown", "zero", "fatal", "window600", "bad_desc", "ends_early")
+
+
+def _ms_role_settings(role: str, c: int):
+    frame = (4000, 3044, 1500, 5000, 2944)[c % 5]
+    if role in ("success", "id_success"):
+        return frame, 1, 3       # a window of 2 frames, rendered to its end by three ticks
+    if role == "ends_early":
+        return frame, 1, 2       # ended by the second tick: the third batch arrives after the end
+    if role in ("window600", "bulk"):
+        return frame, 300, 1000  # a window of 600 frames
+    return frame, 4, 100         # a window of 8 frames
+
+
+def _ms_role_datagrams(role: str, k: int, head: int, cfg, lens, last_batch: bool, bulk_frames: int):
+    """Batch k of one connection: [(kind, seq, length, corrupt)], in completion order. head: its window's head."""
+    _, buffered, final = cfg
+    whole = lambda s: [("data", s, int(ln), False) for ln in lens]
+    if role == "fatal":
+        return [] if k == 0 else whole(head)
+    if role in ("window600", "bulk"):
+        out = []
+        for s in range(head, head + bulk_frames):
+            out += whole(s)
+        return out
+    d = whole(min(head, final + 1) if role in ("success", "id_success") else head)
+    if role == "mismatch_first" and k == 0:
+        d[0] = ("data", head, d[0][2], True)   # the batch's first datagram, and a second exception behind it
+        d.append(("data", head + 1, int(lens[0]), True))
+    elif role == "duplicate":
+        d.append(d[-1])
+    elif role == "dropped":
+        d = d[:-1] if len(d) > 1 else []
+    elif role == "stale_future" and k >= 1:
+        d += [("data", head - 1, int(lens[0]), False), ("data", head + 2 * buffered + 12, int(lens[0]), False),
+              ("data", final + 1, int(lens[-1]), False)]
+    elif role == "id_success" and k == 0:
+        d.insert(0, ("id", 0, 39, False))
+    elif role == "short_unknown" and k == 1:
+        d.insert(1, ("short", 0, 10, False))
+        d.append(("unknown", 0, 100, False))
+    elif role == "unknown" and k == 2:
+        d.insert(len(d) // 2, ("unknown", 0, 64, False))
+    elif role == "unknown_last" and last_batch:
+        d.append(("unknown", 0, 40, False))
+    elif role == "zero" and k == 1:
+        d.insert(0, ("zero", 0, 0, False))
+    elif role == "bad_desc" and k == 0:
+        d.append(("bad", 0, 100, False))
+    elif role == "ends_early" and k == 2:
+        d.append(("zero", 0, 0, False))     # after the end: lowers the slot, changes nothing
+    return d
+
+
+def media_stream_connections(n_conns: int = 37, batches: int = 3, ticks=None, order: str = "conn_major",
+                             roles=None, bulk_frames: int = 2, limit: Optional[int] = None, max_datagram: int = 1472,
+                             mutate_rate: int = 0, seed: int = SEED_CORRUPT, align: int = 1) -> MsConnPlan:
+    """A plan of MediaStream traffic for n_conns device-resident connections: per connection its client settings and a
+    role (MS_CONN_ROLES in turn, the last connection "unknown_last": an exception in the last batch's last datagram;
+    or `roles`), and `batches` batches of datagrams, each followed by ticks[k] render ticks (default 1).
+
+    order: "conn_major" (each connection's datagrams together), "interleaved" (round-robin over the connections, so
+    neighbours differ while more than one connection has datagrams left). A connection's own datagrams keep their
+    order. limit: keep only the first `limit` datagrams of every batch. mutate_rate > 0: about one datagram in
+    mutate_rate of the "bulk" role is made corrupt, short, an ID datagram or stale (seeded).
+    Every batch has an arena of its own with the datagrams packed `align`-byte aligned; a bad descriptor points past it.
+    """
+    from .media_stream import split
+
+    rng = np.random.default_rng(seed)
+    ticks = [1] * batches if ticks is None else list(ticks)
+    if roles is None:
+        roles = [MS_CONN_ROLES[c % len(MS_CONN_ROLES)] for c in range(n_conns)]
+        if n_conns > len(MS_CONN_ROLES):
+            roles[-1] = "unknown_last"
+    settings = [_ms_role_settings(r, c) for c, r in enumerate(roles)]
+    lens = [split(s[0], max_datagram) for s in settings]
+    pattern = _pattern_prefix(max_datagram)
+    out, base, rendered = [], 0, 0
+    for k in range(batches):
+        per_conn = []
+        for c, role in enumerate(roles):
+            head = min(1 + rendered, settings[c][2] + 1)
+            d = _ms_role_datagrams(role, k, head, settings[c], lens[c], k == batches - 1, bulk_frames)
+            if role == "bulk" and mutate_rate > 0:
+                for j in range(len(d)):
+                    if rng.integers(mutate_rate) == 0:
+                        how = int(rng.integers(4))
+                        d[j] = (("data", d[j][1], d[j][2], True), ("short", 0, 7, False), ("id", 0, 60, False),
+                                ("data", 0, d[j][2], False))[how]
+            per_conn.append([(c,) + x for x in d])
+        if order == "conn_major":
+            flat = [x for d in per_conn for x in d]
+        elif order == "interleaved":
+            flat, depth = [], max((len(d) for d in per_conn), default=0)
+            for j in range(depth):
+                flat += [d[j] for d in per_conn if j < len(d)]
+        else:
+            raise ValueError("order %r" % order)
+        if limit is not None:
+            flat = flat[:limit]
+        n = len(flat)
+        descs = np.zeros(n, dtype=DESC_DTYPE)
+        length = np.array([x[3] for x in flat], dtype=np.int64)
+        slot = (length + align - 1) // align * align
+        start = np.cumsum(slot) - slot if n else np.zeros(0, np.int64)
+        arena = np.zeros(int(slot.sum()) + 16, dtype=np.uint8)
+        for i, (c, kind, seq, ln, corrupt) in enumerate(flat):
+            o = int(start[i])
+            if kind == "data":
+                arena[o + 2:o + 10] = np.array([seq], dtype="<i8").view(np.uint8)
+                arena[o + 26:o + ln] = pattern[:ln - 26]
+                if corrupt:
+                    arena[o + 26 + int(rng.integers(ln - 26))] ^= np.uint8(rng.integers(1, 256))
+            elif kind == "id":
+                arena[o:o + 2] = (0x00, 0x10)   # c_udpDatagramProtocolHeaderFlagId, little-endian
+                arena[o + 2:o + ln] = 0x41
+            elif kind == "unknown":
+                arena[o:o + ln] = 0x22
+            elif kind == "bad":
+                start[i] = len(arena) + 1000
+            # "short": ln < 26 zero bytes under flag 0; "zero": no bytes
+        descs["byte_offset"] = start.astype(np.uint64)
+        descs["length"] = length.astype(np.uint32)
+        descs["conn_index"] = np.array([x[0] for x in flat], dtype=np.uint32)
+        descs["skip_head"] = UDP_DATA_HEADER_LENGTH
+        out.append(MsConnBatch(descs, arena, base, ticks[k]))
+        base += n
+        rendered += ticks[k]
+    return MsConnPlan(settings, list(roles), out, max_datagram)
