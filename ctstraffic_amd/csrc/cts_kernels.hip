@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "cts_internal.hpp"
+#include "cts_spans.hpp"
 
 namespace cts {
 
@@ -3007,18 +3008,17 @@ hipError_t launch_refview_strided(uint64_t arena_bytes, uint32_t stride, const u
 }
 
 // cts_refview_accumulate_conns(_strided): refview's grid; every wave of it takes one contiguous span of the batch, a
-// multiple of 64 descriptors
+// multiple of 64 descriptors (span_geometry, cts_spans.hpp)
+static_assert(kSpanBlock == (uint32_t)kBlock && kSpanBlocksPerCu == (uint32_t)kRefviewBlocksPerCu,
+              "span_geometry describes the reference view's grid");
 template <bool STRIDED>
 static hipError_t launch_conn_accumulate_src(uint64_t arena_bytes, const VSource& src, uint32_t n, uint32_t base_index,
                                              const uint32_t* conn_first_fail, uint32_t n_conns, uint64_t* ref_counters,
                                              cts_conn_state* conn_state, hipStream_t stream, const LaunchGeometry& geo)
 {
     if (n == 0) return hipSuccess;
-    const uint64_t want = ((uint64_t)n + kBlock - 1) / kBlock;
-    const uint64_t cap = (uint64_t)(geo.num_cus > 0 ? geo.num_cus : 1) * kRefviewBlocksPerCu;
-    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
-    const uint64_t waves = (uint64_t)grid * (kBlock / 64);
-    const uint32_t span = (uint32_t)((((uint64_t)n + waves - 1) / waves + 63u) / 64u * 64u);
+    const SpanGeometry sg = span_geometry(n, geo.num_cus);
+    const uint32_t grid = sg.grid, span = sg.span;
     if (geo.nontemporal)
         conn_accumulate<true, STRIDED><<<grid, kBlock, 0, stream>>>(arena_bytes, src, n, base_index, conn_first_fail,
                                                                     n_conns, ref_counters, conn_state, span);
@@ -3085,9 +3085,8 @@ hipError_t launch_ms_conn_accumulate(const cts_buf_desc* descs, const cts_datagr
                                      uint64_t* udp_counters, hipStream_t stream, const LaunchGeometry& geo)
 {
     if (n == 0) return hipSuccess;
-    const uint32_t grid = lane_per_item_grid(n, geo);
-    const uint64_t waves = (uint64_t)grid * (kBlock / 64);
-    const uint32_t span = (uint32_t)((((uint64_t)n + waves - 1) / waves + 63u) / 64u * 64u);
+    const SpanGeometry sg = span_geometry(n, geo.num_cus);
+    const uint32_t grid = sg.grid, span = sg.span;
     if (geo.nontemporal)
         ms_conn_accumulate<true><<<grid, kBlock, 0, stream>>>(descs, status, n, base_index, conn_first_fail, conns,
                                                               frame_bytes, frame_elems, n_conns, udp_counters, span);

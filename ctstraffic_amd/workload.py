@@ -538,7 +538,7 @@ class MediaStreamConnectionView:
                 r[f] = e[f][c]
             if e["has_failure"][c]:
                 flags |= MS_CONN_RESULT_FLAG_HAS_FAILURE
-                r["fail_datagram"] = int(e["datagrams"][c]) - 1
+                r["fail_datagram"] = (int(e["datagrams"][c]) - 1) & 0xFFFFFFFF  # a 32-bit field: the low word
             r["first_fail"], r["status"], r["flags"] = self.slots[c], status, flags
             cls = ("successful" if status == 0 else
                    "data_errors" if status == STATUS_ERROR_DATA_DID_NOT_MATCH_BIT_PATTERN else "not_all_data")

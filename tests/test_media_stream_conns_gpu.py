@@ -134,7 +134,9 @@ def test_accumulate_long_spans(engine):
     """Over 2048 x 256 datagrams a wave's span is longer than one tile of 64: runs carried from tile to tile, tiles
     that are nothing but the open run, runs joined across a workgroup's waves. 594 288 synthetic statuses of four
     connections (one long run, an interleaved stretch, blocks of 777), every datagram clean DATA inside a window of
-    600 frames, connection 2 stopped by a preset slot in the blocks; the expectation is computed with numpy masks."""
+    600 frames, connection 2 stopped by a preset slot in the blocks; the expectation is computed with numpy masks.
+    On 256 compute units the span is two tiles, so a parked tile is always a span's last one; spans of five tiles, with
+    parked sums joined inside the loop, are in tests/test_accounting_seams_gpu.py."""
     n, base = 2048 * 256 + 70000, 1000
     i = np.arange(n)
     conn = np.where(i < 300000, 0, np.where(i < 400000, 1 + i % 3, (i // 777) % 4)).astype(np.uint32)
