@@ -5,7 +5,7 @@
 #                      and the tests run
 #                      (tools/libcts_bench_multi.so, tools/pattern_cpu_probe)
 #   make probes     -> the measurement probes of tools/ (ceilings, timelines, ablations; built before an A/B call)
-#   make asm        -> ctstraffic_amd/build/cts_kernels-gfx950.s (disassembly for inspection)
+#   make asm        -> ctstraffic_amd/build/cts_kernels-gfx950.s, cts_accounting-gfx950.s (disassembly for inspection)
 HIPCC     ?= /opt/rocm/bin/hipcc
 ARCH      ?= gfx950
 HIPFLAGS  ?= -O3 -std=c++17 -fPIC -Wall -Wno-unused-result --offload-arch=$(ARCH) -Iinclude -Ictstraffic_amd/csrc
@@ -119,7 +119,7 @@ $(DEVICE_MS_CONNECTIONS): tests/cpp/device_ms_connections.cpp $(ENGINE_SO) $(wil
 # tools/verify_timeline vs verify_timeline_kp alternated on one box, profiles/r04/b/); firmware without the feature
 # runs the compiler's fallback prologue, which loads them as before
 KERNARG_PRELOAD := -mllvm -amdgpu-kernarg-preload-count=16
-ctstraffic_amd/build/cts_kernels.hip.o: HIPFLAGS += $(KERNARG_PRELOAD)
+ctstraffic_amd/build/%.hip.o: HIPFLAGS += $(KERNARG_PRELOAD)
 
 ctstraffic_amd/build/%.o: $(CSRC)/% $(HDRS)
 	@mkdir -p ctstraffic_amd/build
@@ -131,9 +131,11 @@ $(ENGINE_SO): $(OBJS) $(CSRC)/exports.map
 oracle:
 	$(MAKE) -s -C oracle
 
-asm: $(CSRC)/cts_kernels.hip $(HDRS)
+asm: $(patsubst $(CSRC)/%.hip,ctstraffic_amd/build/%-$(ARCH).s,$(wildcard $(CSRC)/*.hip))
+
+ctstraffic_amd/build/%-$(ARCH).s: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p ctstraffic_amd/build
-	$(HIPCC) $(HIPFLAGS) $(KERNARG_PRELOAD) --cuda-device-only -S $< -o ctstraffic_amd/build/cts_kernels-$(ARCH).s
+	$(HIPCC) $(HIPFLAGS) $(KERNARG_PRELOAD) --cuda-device-only -S $< -o $@
 
 clean:
 	rm -rf ctstraffic_amd/build $(ENGINE_SO) $(PROBES) $(BENCH_MULTI) tools/pattern_cpu_probe
