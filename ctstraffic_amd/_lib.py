@@ -223,6 +223,10 @@ def _declare(L: ctypes.CDLL) -> None:
                                          ctypes.POINTER(CtsCountersUdp)], i32),
         "cts_counters_allreduce_udp": ([ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), u32,
                                         ctypes.POINTER(CtsCountersUdp)], i32),
+        "cts_ms_server_init": ([P, P], i32),
+        "cts_media_stream_servers_scratch_bytes": ([u32], ctypes.c_size_t),
+        "cts_media_stream_servers_send": ([P, P, u64, u32, u64, u32, P, u32, P, u32, ctypes.c_int64, ctypes.c_int64,
+                                           P, P, P, P, P, P, ctypes.c_size_t, P], i32),
         "cts_counters_device_bytes": ([], ctypes.c_size_t),
         "cts_counters_reset": ([P, P, P], i32),
         "cts_counters_read": ([P, P, ctypes.POINTER(CtsCounters), P], i32),

@@ -8,6 +8,7 @@
 #include "cts_engine.h"
 #include "cts_media_stream.h"
 #include "cts_media_stream_conns.h"
+#include "cts_media_stream_servers.h"
 
 namespace cts {
 
@@ -195,8 +196,40 @@ hipError_t launch_ms_conn_close(const uint32_t* conn_ids, uint32_t n, uint32_t* 
                                 cts_ms_conn_result* results, uint64_t* close_counters, hipStream_t stream,
                                 const LaunchGeometry& geo);
 
+// MediaStream servers on the device (cts_media_stream_servers.cpp). The planning walks the n listed connections in
+// tiles of kMsServerTile; a tick's scratch holds, in this order, the listed connections' exclusive prefix of wanted
+// slots and its grand total (n + 1 words), the tiles' sums, and a tick block for the caller that passes none.
+constexpr uint32_t kMsServerTile = 256;
+inline uint64_t ms_server_tiles(uint32_t n) { return ((uint64_t)n + kMsServerTile - 1) / kMsServerTile; }
+struct MsServerScratch {
+    uint64_t* prefix;           // n + 1
+    uint64_t* sums;             // ms_server_tiles(n)
+    cts_ms_server_tick* tick;   // 1
+    MsServerScratch(void* base, uint32_t n)
+        : prefix(static_cast<uint64_t*>(base)), sums(prefix + (uint64_t)n + 1),
+          tick(reinterpret_cast<cts_ms_server_tick*>(sums + ms_server_tiles(n)))
+    {
+    }
+    static size_t bytes(uint32_t n)
+    {
+        return (size_t)(((uint64_t)n + 1 + ms_server_tiles(n)) * sizeof(uint64_t) + sizeof(cts_ms_server_tick));
+    }
+};
+// The planning (three launches: tile sums, their scan, apply) writes scratch.prefix, the codes (may be null), `tick`
+// (zeroed first) and the UDP block (may be null), and moves the entries of the connections that fit. The fill reads
+// prefix, the entries and tick->datagrams, and writes the ring from first_slot on, the descriptors and the lengths
+// (either may be null); its grid is launch_media_stream_fill_strided's rule over `capacity`.
+hipError_t launch_ms_server_plan(const uint32_t* conn_ids, uint32_t n, cts_ms_server_state* servers, uint32_t n_conns,
+                                 uint32_t stride, uint32_t capacity, uint32_t* codes, cts_ms_server_tick* tick,
+                                 uint64_t* udp_counters, const MsServerScratch& scratch, hipStream_t stream);
+hipError_t launch_ms_server_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
+                                 uint32_t capacity, const uint32_t* conn_ids, uint32_t n,
+                                 const cts_ms_server_state* servers, uint32_t n_conns, const uint64_t* prefix,
+                                 const cts_ms_server_tick* tick, int64_t qpc, int64_t qpf, cts_buf_desc* descs,
+                                 uint32_t* lengths, hipStream_t stream, const LaunchGeometry& geo);
+
 // The engine's device and launch geometry for the entry points that live outside cts_engine.cpp (cts_refview.cpp,
-// cts_connections.cpp, cts_media_stream_conns.cpp);
+// cts_connections.cpp, cts_media_stream_conns.cpp, cts_media_stream_servers.cpp);
 // e != nullptr. Defined in cts_engine.cpp, where cts_engine is complete.
 const LaunchGeometry& engine_geometry(const cts_engine* e, int* device);
 

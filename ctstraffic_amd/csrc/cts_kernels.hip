@@ -24,6 +24,9 @@
 //   verify_quad_kernel                four buffers per wave (datagram-sized buffers; descriptors or a strided ring)
 //   media_stream_verify_quad_kernel   MediaStream receive: header + payload, four datagrams per wave
 //   fill_kernel / fill_span_kernel / fill_batched_kernel / media_stream_fill_ring_kernel   the sender side
+//   ms_server_sums / _scan / _apply, ms_server_fill   the MediaStream servers' tick: slots planned by a prefix sum over
+//                                     the listed connections, then the ring fill with media_stream_fill_ring_kernel's
+//                                     store loop (cts_ring_store_loop.hpp) and no per-datagram metadata
 //   mailbox_kernel                    SYNC-mode VerifyBuffer without a launch per call (resident grid)
 // The descriptor-only accounting passes (refview_accumulate, conn_accumulate, ms_conn_accumulate and their closes)
 // are in cts_accounting.hip.
@@ -1788,8 +1791,8 @@ __device__ __forceinline__ void ring_chunk_checked(u32x4* ring, uint64_t k, uint
     }
 }
 
-// SCALAR: stride >= 1024, so a round holds at most two datagram starts and the wave tracks its datagram and chunk as
-// wave-uniform values; otherwise each lane finds its own. full_slots: slots wholly inside the arena (clamped to 2^32-1).
+// SCALAR: stride >= 1024 (the two forms of the store loop, cts_ring_store_loop.hpp). full_slots: slots wholly inside
+// the arena (clamped to 2^32-1).
 template <bool NTS, bool SCALAR>
 __global__ void __launch_bounds__(kBlock)
     media_stream_fill_ring_kernel(uint8_t* __restrict__ arena, uint64_t arena_bytes, uint32_t stride,
@@ -1815,46 +1818,278 @@ __global__ void __launch_bounds__(kBlock)
             ls[t] = lengths[d0 + t];
         }
         __syncthreads();
-        // this wave's run of the batch's chunks, whole 64-chunk rounds (the last run may end inside one)
-        const uint32_t nk = nb * cps;
-        const uint32_t per_w = ((nk + WAVES - 1u) / WAVES + 63u) & ~63u;
-        uint32_t kl = wave * per_w;
-        const uint32_t kl1 = kl + per_w < nk ? kl + per_w : nk;
-        const uint64_t kbase = d0 * cps;  // the batch's first ring chunk
-        if constexpr (SCALAR) {
-            if (kl >= kl1) continue;
-            uint32_t ib = kl / cps, cb = kl - ib * cps;  // lane 0's datagram (in the batch) and chunk
-            for (; kl < kl1; kl += 64u) {
-                const bool crosses = cb + 63u >= cps;
-                const uint32_t i1 = ib + 1u < nb ? ib + 1u : ib;
-                const uint32_t l0 = ls[ib], l1 = ls[i1];
-                const bool whole = kl + 64u <= kl1 && l0 == stride && d0 + ib < full_slots &&
-                                   (!crosses || (ib + 1u < nb && l1 == stride && d0 + ib + 1u < full_slots));
-                uint32_t c = cb + lane;
-                const bool second = c >= cps;
-                if (second) c -= cps;
-                if (__builtin_amdgcn_readfirstlane(whole ? 1 : 0)) {
-                    u32x4 e = expected_chunk((16u * c - CTS_UDP_DATA_HEADER_LENGTH) & 0xFFFFu, 0u);
-                    if (cb < 2u) e = header_lanes(e, lane, 0u - cb, hs[ib]);
-                    if (crosses) e = header_lanes(e, lane, cps - cb, hs[i1]);
-                    if constexpr (NTS) __builtin_nontemporal_store(e, ring + kbase + kl + lane);
-                    else ring[kbase + kl + lane] = e;
-                } else if (kl + lane < kl1) {
-                    const uint32_t t = second ? i1 : ib;
-                    ring_chunk_checked<NTS>(ring, kbase + kl + lane, d0 + t, c, ls[t], hs[t], stride, arena_bytes);
-                }
-                cb += 64u;
-                if (cb >= cps) {
-                    cb -= cps;
-                    ++ib;
-                }
-            }
-        } else {  // stride < 1024: several datagrams per round, each lane finds its own
-            for (uint32_t k = kl + lane; k < kl1; k += 64u) {
-                const uint32_t t = k / cps, c = k - t * cps;
-                ring_chunk_checked<NTS>(ring, kbase + k, d0 + t, c, ls[t], hs[t], stride, arena_bytes);
+#include "cts_ring_store_loop.hpp"
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// MediaStream servers on the device (cts_media_stream_servers_send): one tick of the listed connections' frame sends
+// with no per-datagram metadata from the host. Listed connection i wants k_i = datagrams_per_frame ring slots (0 when
+// it sends nothing whatever the room); p_i, the exclusive prefix of the wants in listed order, is its first slot, and
+// it sends when p_i + k_i <= capacity. p is monotonic, so the connections that send are a prefix of those that want
+// and the tick's datagrams are the slots [0, total) with no gap. Three plain launches plan the tick, in tiles of
+// kMsServerTile listed connections (no workgroup ever waits for another):
+//   ms_server_sums    each tile's sum of wants                              -> sums[tile]
+//   ms_server_scan    one workgroup: exclusive scan of the tile sums in place, prefix[n] = the grand total, tick = 0
+//   ms_server_apply   p_i = sums[tile] + the tile's own scan -> prefix[i]; the code, the entry's update, the tick and
+//                     the UDP block of every connection that fits
+// and ms_server_fill writes the ring from prefix[] and the entries.
+// Scratch (MsServerScratch, cts_internal.hpp): u64 prefix[n + 1], u64 sums[tiles], a tick.
+
+// The slots listed connection c wants, and its code when it sends nothing whatever the room.
+__device__ __forceinline__ uint32_t ms_server_want(const cts_ms_server_state* __restrict__ servers, uint32_t c,
+                                                   uint32_t n_conns, uint32_t stride, uint32_t& code)
+{
+    code = CTS_MS_SERVER_SKIPPED;
+    if (c >= n_conns) return 0u;
+    if (servers[c].finished != 0u) {
+        code = CTS_MS_SERVER_ENDED;
+        return 0u;
+    }
+    if (servers[c].datagram_max_size > stride) return 0u;
+    code = CTS_MS_SERVER_SENT;
+    return servers[c].datagrams_per_frame;
+}
+
+// Exclusive scan of v over the workgroup's kBlock threads (wave scans, then the waves' sums through wsum); total = the
+// workgroup's sum. Ends with a barrier: wsum is free again.
+__device__ __forceinline__ uint64_t tile_scan_exclusive(uint64_t v, uint64_t* wsum, uint64_t& total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t inc = v;
+#pragma unroll
+    for (uint32_t off = 1; off < 64u; off <<= 1) {
+        const uint64_t u = (uint64_t)__shfl_up((unsigned long long)inc, off, 64);
+        if (lane >= off) inc += u;
+    }
+    if (lane == 63u) wsum[wave] = inc;
+    __syncthreads();
+    uint64_t base = 0;
+    total = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < (uint32_t)kBlock / 64u; ++w) {
+        if (w < wave) base += wsum[w];
+        total += wsum[w];
+    }
+    __syncthreads();
+    return base + inc - v;
+}
+
+static_assert(kMsServerTile == (uint32_t)kBlock, "one listed connection per thread of a tile");
+
+__global__ void __launch_bounds__(kBlock)
+    ms_server_sums(const uint32_t* __restrict__ ids, uint32_t n, const cts_ms_server_state* __restrict__ servers,
+                   uint32_t n_conns, uint32_t stride, uint64_t* __restrict__ sums)
+{
+    __shared__ uint64_t wsum[kBlock / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * kMsServerTile + threadIdx.x;
+    uint32_t code;
+    const uint64_t want = i < n ? ms_server_want(servers, ids[i], n_conns, stride, code) : 0u;
+    const uint64_t s = wave_sum64(want);
+    if ((threadIdx.x & 63u) == 0u) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint64_t t = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) t += wsum[w];
+        sums[blockIdx.x] = t;
+    }
+}
+
+// One workgroup. tick is 8 dwords (cts_ms_server_tick).
+__global__ void __launch_bounds__(kBlock)
+    ms_server_scan(uint64_t* __restrict__ sums, uint64_t tiles, uint64_t* __restrict__ prefix_total,
+                   uint32_t* __restrict__ tick)
+{
+    __shared__ uint64_t wsum[kBlock / 64];
+    uint64_t carry = 0;
+    for (uint64_t base = 0; base < tiles; base += kBlock) {
+        const uint64_t t = base + threadIdx.x;
+        const uint64_t v = t < tiles ? sums[t] : 0u;
+        uint64_t total;
+        const uint64_t ex = tile_scan_exclusive(v, wsum, total);
+        if (t < tiles) sums[t] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0u) *prefix_total = carry;
+    if (threadIdx.x < sizeof(cts_ms_server_tick) / 4u) tick[threadIdx.x] = 0u;
+}
+
+__global__ void __launch_bounds__(kBlock)
+    ms_server_apply(const uint32_t* __restrict__ ids, uint32_t n, cts_ms_server_state* __restrict__ servers,
+                    uint32_t n_conns, uint32_t stride, uint32_t capacity, const uint64_t* __restrict__ sums,
+                    uint64_t* __restrict__ prefix, uint32_t* __restrict__ codes, cts_ms_server_tick* __restrict__ tick,
+                    uint64_t* __restrict__ udp)
+{
+    __shared__ uint64_t wsum[kBlock / 64];
+    __shared__ uint64_t ctr[kBlock / 64][kCounterCount];
+    __shared__ uint32_t red[kBlock / 64][5];
+    zero_counters<kBlock / 64>(ctr);
+    const uint64_t i = (uint64_t)blockIdx.x * kMsServerTile + threadIdx.x;
+    uint32_t code = CTS_MS_SERVER_SENT, c = 0u;
+    uint64_t want = 0;
+    if (i < n) {
+        c = ids[i];
+        want = ms_server_want(servers, c, n_conns, stride, code);
+    }
+    uint64_t total;
+    const uint64_t p = sums[blockIdx.x] + tile_scan_exclusive(want, wsum, total);
+    uint64_t bytes = 0;
+    uint32_t datagrams = 0, sent = 0, finished = 0, no_room = 0, skipped = 0;
+    if (i < n) {
+        prefix[i] = p;
+        if (code != CTS_MS_SERVER_SENT) {
+            skipped = 1u;
+        } else if (p + want > (uint64_t)capacity) {
+            no_room = 1u;
+            code = CTS_MS_SERVER_NO_ROOM;
+        } else {
+            // the only step that knows whether the connection fits is the one that moves its entry
+            cts_ms_server_state* e = servers + c;
+            bytes = e->frame_size_bytes;
+            datagrams = (uint32_t)want;
+            sent = 1u;
+            e->bits_sent += 8u * bytes;
+            e->datagrams_sent += want;
+            const int64_t next = e->current_frame + 1;
+            e->current_frame = next;
+            if (next > e->final_frame) {
+                e->finished = 1u;
+                finished = 1u;
+                code = CTS_MS_SERVER_FINISHED;
             }
         }
+        if (codes != nullptr) codes[i] = code;
+    }
+    bytes = wave_sum64(bytes);
+    datagrams = wave_sum(datagrams);
+    sent = wave_sum(sent);
+    finished = wave_sum(finished);
+    no_room = wave_sum(no_room);
+    skipped = wave_sum(skipped);
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0u) {
+        // the reference's server adds its sent bits to UdpStatusDetails.m_bitsReceived (ctsIOPattern.cpp:1162)
+        ctr[wave][0] = 8u * bytes;                // cts_counters_udp.bits_received
+        ctr[wave][kCounterCount - 1] = datagrams;  // cts_counters_udp.datagrams
+        red[wave][0] = datagrams;
+        red[wave][1] = sent;
+        red[wave][2] = finished;
+        red[wave][3] = no_room;
+        red[wave][4] = skipped;
+    }
+    flush_counters<kBlock / 64>(udp, ctr);  // barrier first
+    if (threadIdx.x < 5u) {
+        uint32_t s = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) s += red[w][threadIdx.x];
+        uint32_t* const words = &tick->datagrams;  // datagrams, connections_sent, _finished, _no_room, _skipped
+        if (s) atomicAdd(words + threadIdx.x, s);
+    } else if (threadIdx.x == 5u) {
+        uint64_t s = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) s += ctr[w][0];
+        if (s) atomicAdd((unsigned long long*)&tick->bytes, (unsigned long long)(s / 8u));
+    }
+}
+
+// The last i in [lo, hi) with prefix[i] <= g; prefix[lo] <= g.
+__device__ __forceinline__ uint64_t ms_server_listed(const uint64_t* __restrict__ prefix, uint64_t lo, uint64_t hi,
+                                                     uint64_t g)
+{
+    while (hi - lo > 1u) {
+        const uint64_t mid = lo + (hi - lo) / 2u;
+        if (prefix[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// Datagram j of a frame of F bytes in datagrams of at most M, k = ceil(F / M) of them: cts_media_stream_split's
+// lengths in closed form (ctsMediaStreamProtocol.hpp:171-205: a remainder of 1..26 bytes would not hold a header and
+// a byte, so the last datagram takes 27 and the one before it gives them up).
+__device__ __forceinline__ uint32_t ms_server_length(uint32_t F, uint32_t M, uint32_t k, uint32_t j)
+{
+    const uint32_t r = F % (M != 0u ? M : 1u);
+    const bool tiny = r != 0u && r <= CTS_UDP_DATA_HEADER_LENGTH;
+    if (j + 1u == k) return r == 0u ? M : (tiny && k > 1u ? CTS_UDP_DATA_HEADER_LENGTH + 1u : r);
+    if (j + 2u == k && tiny) return M - (CTS_UDP_DATA_HEADER_LENGTH + 1u - r);
+    return M;
+}
+
+// The tick's ring fill: tick-local datagram g goes to slot g of `ring` (the arena from first_slot on). The grid comes
+// from the capacity; the total is read here, and workgroups past it leave at once. Each workgroup takes one contiguous
+// range of datagrams in batches of kRingBatch, as media_stream_fill_ring_kernel does. It finds the listed connection of
+// its first datagram by a binary search of prefix[] and walks forward: every batch loads the kRingBatch + 1 prefixes
+// from its first datagram's connection on into LDS, each thread finds its datagram's connection among them (beyond
+// them, behind a run of connections that send nothing, in prefix[] itself), and the batch's last datagram leaves its
+// connection for the next batch. The batch's lengths and sequence numbers come from the entries by the closed form
+// (apply has moved the entry: the frame sent is current_frame - 1); the descriptors and lengths are written here as
+// coalesced stores, and the store loop loads nothing.
+template <bool NTS, bool SCALAR>
+__global__ void __launch_bounds__(kBlock)
+    ms_server_fill(uint8_t* __restrict__ ring_base, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
+                          const uint32_t* __restrict__ ids, uint32_t n,
+                          const cts_ms_server_state* __restrict__ servers, const uint64_t* __restrict__ prefix,
+                          const cts_ms_server_tick* __restrict__ tick, uint64_t qpc, uint64_t qpf,
+                          cts_buf_desc* __restrict__ descs, uint32_t* __restrict__ lengths, uint32_t full_slots,
+                          uint32_t capacity, uint32_t n_conns)
+{
+    constexpr uint32_t WAVES = kBlock / 64;
+    __shared__ RingHeader hs[kRingBatch];
+    __shared__ uint32_t ls[kRingBatch];
+    __shared__ uint64_t ps[kRingBatch + 1];
+    __shared__ uint64_t first_listed;
+    // (the clamp, and the id check below, only matter to a caller who lists a connection twice: nothing is written
+    // outside the capacity or read outside the table then either)
+    const uint32_t total = tick->datagrams < capacity ? tick->datagrams : capacity;
+    if (total == 0u) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t cps = stride >> 4;  // chunks per slot
+    // at least a batch's worth of datagrams per workgroup, or all of them
+    const uint32_t even = (uint32_t)(((uint64_t)total + gridDim.x - 1u) / gridDim.x);
+    const uint32_t least = total < kRingBatch ? total : kRingBatch;
+    const uint32_t per_wg = even > least ? even : least;
+    const uint64_t g0 = (uint64_t)blockIdx.x * per_wg;
+    if (g0 >= total) return;
+    const uint64_t g1 = g0 + per_wg < total ? g0 + per_wg : total;
+    if (threadIdx.x == 0u) first_listed = ms_server_listed(prefix, 0u, n, g0);
+    u32x4* const ring = reinterpret_cast<u32x4*>(ring_base);
+    for (uint64_t d0 = g0; d0 < g1; d0 += kRingBatch) {
+        const uint32_t nb = (uint32_t)(g1 - d0 < kRingBatch ? g1 - d0 : kRingBatch);
+        __syncthreads();  // every wave is done with the previous batch's LDS
+        const uint64_t i0 = first_listed;
+        for (uint32_t t = threadIdx.x; t <= kRingBatch; t += kBlock) ps[t] = prefix[i0 + t < n ? i0 + t : n];
+        __syncthreads();
+        for (uint32_t t = threadIdx.x; t < nb; t += kBlock) {
+            const uint64_t g = d0 + t;
+            uint32_t lo = 0u, hi = kRingBatch + 1u;  // the last w with ps[w] <= g; ps[0] <= d0
+            while (hi - lo > 1u) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (ps[mid] <= g) lo = mid;
+                else hi = mid;
+            }
+            uint64_t i = i0 + lo, p = ps[lo];
+            if (lo == kRingBatch && i + 1u < n) {
+                i = ms_server_listed(prefix, i, n, g);
+                p = prefix[i];
+            }
+            if (i >= n) i = n - 1u;  // (never, unless a connection is listed twice)
+            const uint32_t c = ids[i];
+            const cts_ms_server_state* e = servers + (c < n_conns ? c : 0u);
+            const uint32_t len = c >= n_conns ? 0u
+                                              : ms_server_length(e->frame_size_bytes, e->datagram_max_size,
+                                                                 e->datagrams_per_frame, (uint32_t)(g - p));
+            hs[t] = RingHeader{(uint64_t)(e->current_frame - 1), qpc, qpf};
+            ls[t] = len;
+            if (descs != nullptr)
+                descs[g] = cts_buf_desc{(first_slot + g) * stride, len, 0u, c, CTS_UDP_DATA_HEADER_LENGTH};
+            if (lengths != nullptr) lengths[g] = len;
+            if (t == nb - 1u) first_listed = i;
+        }
+        __syncthreads();
+#include "cts_ring_store_loop.hpp"
     }
 }
 
@@ -2398,6 +2633,57 @@ hipError_t launch_media_stream_fill_strided(uint8_t* arena, uint64_t arena_bytes
         else CTS_RING_FILL(false, false);
     }
 #undef CTS_RING_FILL
+    return hipGetLastError();
+}
+
+// cts_media_stream_servers_send's planning: three launches, the middle one a single workgroup
+hipError_t launch_ms_server_plan(const uint32_t* conn_ids, uint32_t n, cts_ms_server_state* servers, uint32_t n_conns,
+                                 uint32_t stride, uint32_t capacity, uint32_t* codes, cts_ms_server_tick* tick,
+                                 uint64_t* udp_counters, const MsServerScratch& scratch, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    const uint64_t tiles = ms_server_tiles(n);
+    ms_server_sums<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, servers, n_conns, stride, scratch.sums);
+    ms_server_scan<<<1, kBlock, 0, stream>>>(scratch.sums, tiles, scratch.prefix + n,
+                                             reinterpret_cast<uint32_t*>(tick));
+    ms_server_apply<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, servers, n_conns, stride, capacity,
+                                                            scratch.sums, scratch.prefix, codes, tick, udp_counters);
+    return hipGetLastError();
+}
+
+// the tick's ring fill: launch_media_stream_fill_strided's grid rule over the capacity (the total is on the device)
+hipError_t launch_ms_server_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
+                                 uint32_t capacity, const uint32_t* conn_ids, uint32_t n,
+                                 const cts_ms_server_state* servers, uint32_t n_conns, const uint64_t* prefix,
+                                 const cts_ms_server_tick* tick, int64_t qpc, int64_t qpf, cts_buf_desc* descs,
+                                 uint32_t* lengths, hipStream_t stream, const LaunchGeometry& geo)
+{
+    if (n == 0 || capacity == 0) return hipSuccess;
+    if ((stride & 15u) != 0u || stride < 32u || stride > (1u << 20) || ((uintptr_t)arena & 15u) != 0u ||
+        first_slot > arena_bytes / stride)
+        return hipErrorInvalidValue;
+    const uint64_t cap = (uint64_t)geo.num_cus * (uint64_t)(geo.ring_fill_blocks_per_cu > 0 ? geo.ring_fill_blocks_per_cu : 4);
+    const uint64_t want = ((uint64_t)capacity + kRingBatch - 1) / kRingBatch;
+    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    // the ring the kernel sees starts at first_slot: its slot g is the tick's datagram g
+    uint8_t* const ring = arena + first_slot * stride;
+    const uint64_t ring_bytes = arena_bytes - first_slot * stride;
+    const uint64_t slots = ring_bytes / stride;
+    const uint32_t full_slots = (uint32_t)(slots < 0xFFFFFFFFull ? slots : 0xFFFFFFFFull);
+    const bool nts = geo.fill_nt != 0;
+#define CTS_SERVER_FILL(NT_, SC_)                                                                                   \
+    ms_server_fill<NT_, SC_><<<grid, kBlock, 0, stream>>>(ring, ring_bytes, stride, first_slot, conn_ids, n, \
+                                                                 servers, prefix, tick, (uint64_t)qpc,              \
+                                                                 (uint64_t)qpf, descs, lengths, full_slots, capacity,    \
+                                                                 n_conns)
+    if (stride >= 1024u) {
+        if (nts) CTS_SERVER_FILL(true, true);
+        else CTS_SERVER_FILL(false, true);
+    } else {
+        if (nts) CTS_SERVER_FILL(true, false);
+        else CTS_SERVER_FILL(false, false);
+    }
+#undef CTS_SERVER_FILL
     return hipGetLastError();
 }
 

@@ -490,3 +490,121 @@ class ConnectionTable:
 
     def read_udp(self, stream=None) -> dict:
         return self.engine.read_counters_udp(self.udp, stream=stream)
+
+
+# ---- MediaStream servers on the device-resident path (include/cts_media_stream_servers.h) ------------------------
+def server_init(frame_size_bytes: int, datagram_max_size: int, stream_length_frames: int,
+                frames_per_second: int = 60) -> np.ndarray:
+    """cts_ms_server_init: a fresh cts_ms_server_state (one MS_SERVER_STATE_DTYPE record) for a server with these
+    settings. Raises CtsError where the settings are refused (a frame of at most 26 bytes, a datagram_max_size below
+    53: the device's own rule)."""
+    from .types import MS_SERVER_STATE_DTYPE
+
+    s = Settings(frame_size_bytes, datagram_max_size, frames_per_second, 0, stream_length_frames)
+    out = np.zeros(1, dtype=MS_SERVER_STATE_DTYPE)
+    check("cts_ms_server_init", lib().cts_ms_server_init(ctypes.addressof(s), out.ctypes.data))
+    return out[0]
+
+
+def servers_scratch_bytes(n: int) -> int:
+    """cts_media_stream_servers_scratch_bytes: the scratch a tick over n listed connections needs."""
+    return int(lib().cts_media_stream_servers_scratch_bytes(n))
+
+
+def servers_send(engine, arena, stride: int, first_slot: int, capacity: int, conn_ids, servers, n_conns: int, qpc: int,
+                 qpf: int, scratch, descs=None, lengths=None, codes=None, tick=None, udp_counters=None, stream=None,
+                 n: int = None, arena_bytes: int = None, scratch_bytes: int = None) -> None:
+    """cts_media_stream_servers_send: one tick of the connections conn_ids (uint32/int32 device tensor, distinct) into
+    slots first_slot .. of arena. descs (24 bytes per slot of the capacity), lengths, codes (4 bytes each), tick (32
+    bytes) and udp_counters are device tensors or None. Raises CtsError(CTS_E_INVALID) for a refused argument."""
+    from .engine import _nbytes, _stream
+
+    n = _nbytes(conn_ids) // 4 if n is None else n
+    check("cts_media_stream_servers_send",
+          engine._L.cts_media_stream_servers_send(
+              engine._h, _ptr(arena), _nbytes(arena) if arena_bytes is None else arena_bytes, stride, first_slot,
+              capacity, _ptr(conn_ids), n, _ptr(servers), n_conns, qpc, qpf, _ptr(descs), _ptr(lengths), _ptr(codes),
+              _ptr(tick), _ptr(udp_counters), _ptr(scratch),
+              _nbytes(scratch) if scratch_bytes is None else scratch_bytes, _stream(stream)))
+
+
+class ServerTable:
+    """Many MediaStream servers on one device: the entry table, a tick's scratch, the datagram ring with its
+    descriptors and lengths, the codes, the tick block and the UDP block, with the tick as a method.
+
+    settings: (frame_size_bytes, datagram_max_size, stream_length_frames) per connection slot. The ring holds
+    ring_slots slots of stride bytes (pre-filled with `fill`), a tick writes at most capacity of them from first_slot
+    on. :meth:`send` is one frame of the listed connections; ``descs_of(n)`` is the descriptor array of the tick's
+    first n datagrams for :meth:`ConnectionTable.verify` and :meth:`ConnectionTable.accumulate`, with n computed from
+    the settings (``datagrams_per_tick``): nothing is read back between the send and the receive pass."""
+
+    def __init__(self, engine, settings, stride: int, capacity: int, ring_slots: int = None, device=None,
+                 fill: int = 0, max_listed: int = None):
+        import torch
+
+        from .types import MS_SERVER_STATE_DTYPE, MS_SERVER_TICK_DTYPE
+
+        self.engine = engine
+        self.device = device or "cuda:%d" % engine.device
+        self.fresh = np.zeros(len(settings), dtype=MS_SERVER_STATE_DTYPE)
+        for c, (frame_size, datagram_max, length) in enumerate(settings):
+            self.fresh[c] = server_init(frame_size, datagram_max, length)
+        self.n_conns, self.stride, self.capacity = len(settings), stride, capacity
+        self.ring_slots = capacity if ring_slots is None else ring_slots
+        words = max(1, self.n_conns) * (MS_SERVER_STATE_DTYPE.itemsize // 8)
+        self.servers = torch.zeros(words, dtype=torch.int64, device=self.device)
+        if self.n_conns:
+            self.servers.copy_(torch.from_numpy(self.fresh.view(np.int64).copy()))
+        self.max_listed = max(1, self.n_conns if max_listed is None else max_listed)
+        self.scratch = torch.zeros((servers_scratch_bytes(self.max_listed) + 7) // 8, dtype=torch.int64,
+                                   device=self.device)
+        self.ring = torch.full((max(16, self.ring_slots * stride),), fill, dtype=torch.uint8, device=self.device)
+        self.descs = torch.zeros(max(1, capacity) * (DESC_DTYPE.itemsize // 8), dtype=torch.int64, device=self.device)
+        self.lengths = torch.zeros(max(1, capacity), dtype=torch.int32, device=self.device)
+        self.codes = torch.zeros(self.max_listed, dtype=torch.int32, device=self.device)
+        self.tick = torch.zeros(MS_SERVER_TICK_DTYPE.itemsize // 8, dtype=torch.int64, device=self.device)
+        self.udp = engine.new_counters()
+
+    def datagrams_per_tick(self, conn_ids) -> int:
+        """The datagrams one tick of these (host) ids writes while all of them run and fit: the receive pass's n."""
+        return int(sum(int(self.fresh["datagrams_per_frame"][c]) for c in conn_ids))
+
+    def send(self, conn_ids, qpc: int, qpf: int, first_slot: int = 0, stream=None) -> None:
+        """One tick of conn_ids (uint32/int32 device tensor, distinct, at most max_listed of them)."""
+        from .engine import _nbytes
+
+        n = _nbytes(conn_ids) // 4
+        if n > self.codes.numel():
+            raise ValueError("%d ids listed, the table's codes and scratch hold %d" % (n, self.codes.numel()))
+        servers_send(self.engine, self.ring, self.stride, first_slot, self.capacity, conn_ids, self.servers,
+                     self.n_conns, qpc, qpf, self.scratch, descs=self.descs, lengths=self.lengths, codes=self.codes,
+                     tick=self.tick, udp_counters=self.udp, stream=stream)
+
+    def load(self, entries: np.ndarray) -> None:
+        """Write entries (MS_SERVER_STATE_DTYPE[n_conns]) over the table: a stream resumed, or a test's preset."""
+        import torch
+
+        e = np.ascontiguousarray(entries, dtype=self.fresh.dtype)
+        if len(e) != self.n_conns:
+            raise ValueError("%d entries for a table of %d" % (len(e), self.n_conns))
+        if self.n_conns:
+            self.servers.copy_(torch.from_numpy(e.view(np.int64).copy()))
+
+    def descs_of(self, n: int):
+        """The descriptors of the last tick's first n datagrams (a view)."""
+        return self.descs[: n * (DESC_DTYPE.itemsize // 8)]
+
+    def read(self):
+        """(entries MS_SERVER_STATE_DTYPE, codes uint32, tick: one MS_SERVER_TICK_DTYPE record) copied to the host."""
+        from .types import MS_SERVER_TICK_DTYPE
+
+        return (self.servers.cpu().numpy().view(self.fresh.dtype)[: self.n_conns],
+                self.codes.cpu().numpy().view(np.uint32), self.tick.cpu().numpy().view(MS_SERVER_TICK_DTYPE)[0])
+
+    def read_ring(self):
+        """(ring bytes, descriptors DESC_DTYPE[capacity], lengths uint32[capacity]) copied to the host."""
+        return (self.ring.cpu().numpy(), self.descs.cpu().numpy().view(DESC_DTYPE)[: self.capacity],
+                self.lengths.cpu().numpy().view(np.uint32)[: self.capacity])
+
+    def read_udp(self, stream=None) -> dict:
+        return self.engine.read_counters_udp(self.udp, stream=stream)

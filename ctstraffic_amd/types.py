@@ -128,3 +128,32 @@ MS_CONN_RUNNING, MS_CONN_FINISHED, MS_CONN_FATAL, MS_CONN_CLOSED = 0, 1, 2, 3
 # cts_counters_udp: the six words of a UDP block
 UDP_FIELDS = ("bits_received", "successful_frames", "dropped_frames", "duplicate_frames", "error_frames", "datagrams")
 assert MS_CONN_STATE_DTYPE.itemsize == 112 and MS_CONN_RESULT_DTYPE.itemsize == 88
+# cts_ms_server_state (include/cts_media_stream_servers.h): one MediaStream server's device entry
+MS_SERVER_STATE_DTYPE = np.dtype(
+    [
+        ("bits_sent", "<u8"),
+        ("datagrams_sent", "<u8"),
+        ("current_frame", "<i8"),
+        ("final_frame", "<i8"),
+        ("frame_size_bytes", "<u4"),
+        ("datagram_max_size", "<u4"),
+        ("datagrams_per_frame", "<u4"),
+        ("finished", "<u4"),
+    ]
+)
+# cts_ms_server_tick: what one cts_media_stream_servers_send did
+MS_SERVER_TICK_DTYPE = np.dtype(
+    [
+        ("bytes", "<u8"),
+        ("datagrams", "<u4"),
+        ("connections_sent", "<u4"),
+        ("connections_finished", "<u4"),
+        ("connections_no_room", "<u4"),
+        ("connections_skipped", "<u4"),
+        ("reserved", "<u4"),
+    ]
+)
+# a tick's per-connection codes
+MS_SERVER_SENT, MS_SERVER_FINISHED, MS_SERVER_ENDED, MS_SERVER_NO_ROOM, MS_SERVER_SKIPPED = 0, 1, 2, 3, 4
+MS_SERVER_MIN_DATAGRAM = 53  # CTS_MS_SERVER_MIN_DATAGRAM
+assert MS_SERVER_STATE_DTYPE.itemsize == 48 and MS_SERVER_TICK_DTYPE.itemsize == 32

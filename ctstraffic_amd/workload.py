@@ -733,3 +733,126 @@ def media_stream_connections(n_conns: int = 37, batches: int = 3, ticks=None, or
         base += n
         rendered += ticks[k]
     return MsConnPlan(settings, list(roles), out, max_datagram)
+
+
+# ---- MediaStream servers on the device-resident path (include/cts_media_stream_servers.h) ---------------------
+MS_SERVER_TICK_FIELDS = ("bytes", "datagrams", "connections_sent", "connections_finished", "connections_no_room",
+                         "connections_skipped")
+
+
+def media_stream_server_entries(settings):
+    """cts_ms_server_init as a model, for a list of (frame_size_bytes, datagram_max_size, stream_length_frames).
+    Returns MS_SERVER_STATE_DTYPE[len(settings)]; raises ValueError where cts_ms_server_init returns CTS_E_INVALID."""
+    from .types import MS_SERVER_MIN_DATAGRAM, MS_SERVER_STATE_DTYPE
+
+    e = np.zeros(len(settings), dtype=MS_SERVER_STATE_DTYPE)
+    for c, (frame_size, datagram_max, length) in enumerate(settings):
+        if frame_size <= UDP_DATA_HEADER_LENGTH or length <= 0 or length > 0xFFFFFFFF:
+            raise ValueError("connection %d: frame size %d, stream length %d" % (c, frame_size, length))
+        if datagram_max < MS_SERVER_MIN_DATAGRAM:
+            raise ValueError("connection %d: datagrams of at most %d bytes" % (c, datagram_max))
+        e[c]["current_frame"] = 1
+        e[c]["final_frame"] = length
+        e[c]["frame_size_bytes"] = frame_size
+        e[c]["datagram_max_size"] = datagram_max
+        e[c]["datagrams_per_frame"] = -(-frame_size // datagram_max)
+    return e
+
+
+def media_stream_frame_lengths(frame_size: int, datagram_max: int) -> list:
+    """cts_media_stream_split's lengths in closed form, as the device computes them: with k = ceil(F / M) and r =
+    F mod M a remainder of 1..26 bytes makes the last datagram 27 bytes and the one before it M - (27 - r)."""
+    F, M = int(frame_size), int(datagram_max)
+    k, r = -(-F // M), F % M
+    lens = [M] * k
+    tiny = 0 < r <= UDP_DATA_HEADER_LENGTH
+    if k >= 2 and tiny:
+        lens[k - 2] = M - (UDP_DATA_HEADER_LENGTH + 1 - r)
+    lens[k - 1] = M if r == 0 else (UDP_DATA_HEADER_LENGTH + 1 if tiny and k > 1 else r)
+    return lens
+
+
+def media_stream_datagram(length: int, seq: int, qpc: int, qpf: int) -> np.ndarray:
+    """One data datagram's bytes: the packed 26-byte header {u16 0, i64 seq, i64 qpc, i64 qpf} and P[0 .. length - 26)."""
+    import struct
+
+    d = np.empty(length, dtype=np.uint8)
+    d[:UDP_DATA_HEADER_LENGTH] = np.frombuffer(struct.pack("<Hqqq", 0, seq, qpc, qpf), dtype=np.uint8)
+    d[UDP_DATA_HEADER_LENGTH:] = _pattern_prefix(length - UDP_DATA_HEADER_LENGTH)
+    return d
+
+
+class MediaStreamServerView:
+    """The device-resident MediaStream servers as a model, one connection at a time in Python integers: what
+    cts_media_stream_servers_send does to the entries, the codes, the tick block, the UDP block, the ring, the
+    descriptors and the lengths. ring is the caller's array of bytes (what the device ring held before the tick);
+    slots the tick does not write keep their bytes, descriptors and lengths beyond the tick's datagrams theirs."""
+
+    def __init__(self, entries: np.ndarray, stride: int, ring: np.ndarray, capacity: int):
+        from .types import MS_SERVER_STATE_DTYPE
+
+        self.entries = np.array(entries, dtype=MS_SERVER_STATE_DTYPE, copy=True)
+        self.n_conns, self.stride, self.capacity = len(self.entries), stride, capacity
+        self.ring = np.array(ring, dtype=np.uint8, copy=True)
+        self.descs = np.zeros(capacity, dtype=DESC_DTYPE)
+        self.lengths = np.zeros(capacity, dtype=np.uint32)
+        self.udp = dict.fromkeys(UDP_FIELDS, 0)
+        self.codes = np.zeros(0, dtype=np.uint32)
+        self.tick = dict.fromkeys(MS_SERVER_TICK_FIELDS, 0)
+
+    def send(self, conn_ids, qpc: int, qpf: int, first_slot: int = 0, capacity: int = None):
+        """One tick of the distinct connections conn_ids. Returns (codes, tick)."""
+        from .media_stream import split
+
+        capacity = self.capacity if capacity is None else capacity
+        e, tick = self.entries, dict.fromkeys(MS_SERVER_TICK_FIELDS, 0)
+        codes, p = np.zeros(len(conn_ids), dtype=np.uint32), 0
+        for i, c in enumerate(int(x) for x in conn_ids):
+            if c >= self.n_conns or int(e["finished"][c]) != 0 or int(e["datagram_max_size"][c]) > self.stride:
+                codes[i] = 2 if c < self.n_conns and int(e["finished"][c]) != 0 else 4
+                tick["connections_skipped"] += 1
+                continue
+            F, M, k = (int(e[f][c]) for f in ("frame_size_bytes", "datagram_max_size", "datagrams_per_frame"))
+            first, p = p, p + k
+            if first + k > capacity:
+                codes[i] = 3
+                tick["connections_no_room"] += 1
+                continue
+            lens = [int(x) for x in split(F, M)]
+            assert len(lens) == k and sum(lens) == F  # a frame's bytes include its datagrams' headers
+            seq = int(e["current_frame"][c])
+            # the leading run of equal lengths as one block of rows, the rest one datagram at a time
+            run = next((j for j, x in enumerate(lens) if x != lens[0]), k)
+            s0 = first_slot + first
+            if len(self.ring) % self.stride == 0:
+                self.ring.reshape(-1, self.stride)[s0:s0 + run, :lens[0]] = media_stream_datagram(lens[0], seq, qpc, qpf)
+            else:
+                run = 0
+            for j in range(run, k):
+                o = (s0 + j) * self.stride
+                self.ring[o:o + lens[j]] = media_stream_datagram(lens[j], seq, qpc, qpf)
+            d = self.descs[first:first + k]
+            d["byte_offset"] = (s0 + np.arange(k, dtype=np.uint64)) * np.uint64(self.stride)
+            d["length"], d["expected_pattern_offset"], d["conn_index"], d["skip_head"] = lens, 0, c, UDP_DATA_HEADER_LENGTH
+            self.lengths[first:first + k] = lens
+            e["bits_sent"][c] = int(e["bits_sent"][c]) + 8 * F
+            e["datagrams_sent"][c] = int(e["datagrams_sent"][c]) + k
+            e["current_frame"][c] = seq + 1
+            if seq + 1 > int(e["final_frame"][c]):
+                e["finished"][c] = 1
+                tick["connections_finished"] += 1
+                codes[i] = 1
+            tick["bytes"] += F
+            tick["datagrams"] += k
+            tick["connections_sent"] += 1
+            self.udp["bits_received"] += 8 * F
+            self.udp["datagrams"] += k
+        self.codes, self.tick = codes, tick
+        return codes, tick
+
+
+def media_stream_server_view(entries: np.ndarray, stride: int, ring: np.ndarray,
+                             capacity: int) -> MediaStreamServerView:
+    """A model of the device-resident MediaStream servers over `entries` (media_stream_server_entries) and a ring of
+    stride-byte slots; see MediaStreamServerView."""
+    return MediaStreamServerView(entries, stride, ring, capacity)
