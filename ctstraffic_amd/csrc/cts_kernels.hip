@@ -39,6 +39,7 @@
 #include <type_traits>
 
 #include "cts_device_util.hpp"
+#include "cts_grids.hpp"
 #include "cts_internal.hpp"
 
 namespace cts {
@@ -2094,40 +2095,22 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // ---------------------------------------------------------------------------------------------
+// The grid rules are cts_grids.hpp's (plain integers, shared with the tests' model of the loop depths); these pick each
+// path's blocks-per-CU value out of the launch geometry.
 static inline uint32_t grid_for(uint32_t n, int teams_per_block, const LaunchGeometry& geo, int bpc_cap = 0)
 {
-    const uint64_t want = ((uint64_t)n + teams_per_block - 1) / teams_per_block;
     const int bpc = bpc_cap > 0 ? bpc_cap : (teams_per_block > 1 ? geo.small_blocks_per_cu : geo.blocks_per_cu);
-    const uint64_t cap = (uint64_t)geo.num_cus * (uint64_t)(bpc > 0 ? bpc : 8);
-    // grid-stride with the same number of teams' worth of work per workgroup: past the cap
-    // the grid shrinks to ceil(want / per) so no workgroup runs one buffer more than the
-    // rest (an uneven split, e.g. 4096 buffers over 1280 workgroups, leaves a tail of
-    // workgroups with an extra buffer that alone sets the launch's end)
-    const uint64_t per = want <= cap ? 1 : (want + cap - 1) / cap;
-    const uint64_t g = (want + per - 1) / per;
-    return (uint32_t)(g == 0 ? 1 : g);
+    return grid_for(n, teams_per_block, geo.num_cus, bpc);
 }
 
+static_assert(kGridBlock == (uint32_t)kBlock && kGridQuadTeams == (uint32_t)(kBlock / kQuadTeam) &&
+                  kGridFillPiece == kFillPiece && kGridFillBatch == kFillBatch && kGridRingBatch == kRingBatch,
+              "cts_grids.hpp sizes the launches of these kernels");
 
-
-// Chunked launch of a four-buffers-per-wave kernel (QuadWalk): chunk = geo.small_chunk
-// buffers (rounded up to the block's 16 teams); 0 = one block-contiguous range per block, every
-// block but the last with the same count.
-struct ContigGrid {
-    uint32_t grid, per;
-};
+// Chunked launch of a four-buffers-per-wave kernel (QuadWalk): chunk = geo.small_chunk buffers
 static inline ContigGrid contig_grid(uint32_t n, const LaunchGeometry& geo)
 {
-    const uint32_t teams = kBlock / kQuadTeam;
-    const uint32_t g = grid_for(n, teams, geo);
-    if (geo.small_chunk > 0) {
-        const uint64_t per = ((uint64_t)geo.small_chunk + teams - 1) / teams * teams;
-        const uint64_t chunks = ((uint64_t)n + per - 1) / per;
-        return ContigGrid{(uint32_t)(chunks < g ? chunks : g), (uint32_t)per};
-    }
-    const uint64_t groups = ((uint64_t)n + teams - 1) / teams;
-    const uint64_t per = (groups + g - 1) / g * teams;
-    return ContigGrid{(uint32_t)(((uint64_t)n + per - 1) / per), (uint32_t)per};
+    return contig_grid(n, geo.num_cus, geo.small_blocks_per_cu, geo.small_chunk);
 }
 
 template <bool NT>
@@ -2443,14 +2426,6 @@ hipError_t launch_verify_strided(const uint8_t* arena, uint64_t arena_bytes, uin
                                     counters, conn_first_fail, n_conns, 0u, stream, geo);
 }
 
-// grid of the batched datagram fills: whole batches per workgroup, at most ring_fill_blocks_per_cu per CU
-static inline uint32_t batched_fill_grid(uint32_t n, const LaunchGeometry& geo)
-{
-    const uint64_t cap = (uint64_t)geo.num_cus * (uint64_t)(geo.ring_fill_blocks_per_cu > 0 ? geo.ring_fill_blocks_per_cu : 4);
-    const uint64_t want = ((uint64_t)n + kFillBatch - 1) / kFillBatch;
-    return (uint32_t)(want < cap ? want : cap);
-}
-
 hipError_t launch_fill(uint8_t* arena, uint64_t arena_bytes, const cts_buf_desc* descs, uint32_t n,
                        uint32_t max_length_hint, hipStream_t stream, const LaunchGeometry& geo)
 {
@@ -2461,12 +2436,9 @@ hipError_t launch_fill(uint8_t* arena, uint64_t arena_bytes, const cts_buf_desc*
     const bool nts = geo.fill_nt == 2 ? small : geo.fill_nt != 0;
     const uint32_t sgrid = grid_for(n, kBlock / 64, geo), lgrid = grid_for(n, 1, geo, geo.fill_blocks_per_cu);
     if (!small && max_length_hint != 0) {  // the workgroup path in piece order (fill_pieces_kernel)
-        const uint32_t ppb = (uint32_t)(((uint64_t)max_length_hint + kFillPiece - 1) / kFillPiece);
-        const uint64_t total = (uint64_t)n * ppb;
-        const uint64_t cap = (uint64_t)geo.num_cus * (uint64_t)(geo.fill_blocks_per_cu > 0 ? geo.fill_blocks_per_cu : 1);
-        const uint32_t pgrid = (uint32_t)(total < cap ? total : cap);
-        if (nts) fill_pieces_kernel<true><<<pgrid, kBlock, 0, stream>>>(arena, arena_bytes, descs, n, ppb);
-        else fill_pieces_kernel<false><<<pgrid, kBlock, 0, stream>>>(arena, arena_bytes, descs, n, ppb);
+        const PieceGrid pg = piece_fill_grid(n, max_length_hint, geo.num_cus, geo.fill_blocks_per_cu);
+        if (nts) fill_pieces_kernel<true><<<pg.grid, kBlock, 0, stream>>>(arena, arena_bytes, descs, n, pg.ppb);
+        else fill_pieces_kernel<false><<<pg.grid, kBlock, 0, stream>>>(arena, arena_bytes, descs, n, pg.ppb);
         return hipGetLastError();
     }
     if (nts) {
@@ -2601,7 +2573,7 @@ hipError_t launch_media_stream_fill(uint8_t* arena, uint64_t arena_bytes, const 
     // store policy: fill_nt 0 or 2 (by path) = plain, 1 = nontemporal (batched: 5.08 ms plain vs 5.37 nt per 16 M x
     // 1472 B, tools/ring_fill_probe.hip)
     const bool nts = geo.fill_nt == 1;
-    const uint32_t grid = batched_fill_grid(n, geo);
+    const uint32_t grid = batched_fill_grid(n, geo.num_cus, geo.ring_fill_blocks_per_cu);
     if (nts) fill_batched_kernel<true><<<grid, kBlock, 0, stream>>>(arena, arena_bytes, descs, headers, n);
     else fill_batched_kernel<false><<<grid, kBlock, 0, stream>>>(arena, arena_bytes, descs, headers, n);
     return hipGetLastError();
@@ -2615,10 +2587,8 @@ hipError_t launch_media_stream_fill_strided(uint8_t* arena, uint64_t arena_bytes
     // (stride <= 1 MiB keeps a batch's chunk count, 512 x stride / 16, in 32 bits; a UDP datagram is < 64 KiB)
     if ((stride & 15u) != 0u || stride < 32u || stride > (1u << 20) || ((uintptr_t)arena & 15u) != 0u)
         return hipErrorInvalidValue;
-    const uint64_t cap = (uint64_t)geo.num_cus * (uint64_t)(geo.ring_fill_blocks_per_cu > 0 ? geo.ring_fill_blocks_per_cu : 4);
     // every workgroup gets at least a batch's worth of datagrams, or the whole ring
-    const uint64_t want = ((uint64_t)n + kRingBatch - 1) / kRingBatch;
-    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    const uint32_t grid = ring_fill_grid(n, geo.num_cus, geo.ring_fill_blocks_per_cu);
     const uint64_t slots = arena_bytes / stride;
     const uint32_t full_slots = (uint32_t)(slots < 0xFFFFFFFFull ? slots : 0xFFFFFFFFull);
     const bool nts = geo.fill_nt != 0;
@@ -2662,9 +2632,7 @@ hipError_t launch_ms_server_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t 
     if ((stride & 15u) != 0u || stride < 32u || stride > (1u << 20) || ((uintptr_t)arena & 15u) != 0u ||
         first_slot > arena_bytes / stride)
         return hipErrorInvalidValue;
-    const uint64_t cap = (uint64_t)geo.num_cus * (uint64_t)(geo.ring_fill_blocks_per_cu > 0 ? geo.ring_fill_blocks_per_cu : 4);
-    const uint64_t want = ((uint64_t)capacity + kRingBatch - 1) / kRingBatch;
-    const uint32_t grid = (uint32_t)(want < cap ? want : cap);
+    const uint32_t grid = ring_fill_grid(capacity, geo.num_cus, geo.ring_fill_blocks_per_cu);
     // the ring the kernel sees starts at first_slot: its slot g is the tick's datagram g
     uint8_t* const ring = arena + first_slot * stride;
     const uint64_t ring_bytes = arena_bytes - first_slot * stride;

@@ -213,6 +213,40 @@ def test_several_batches_per_workgroup():
         eng.close()
 
 
+def test_several_batches_per_workgroup_wide_slots():
+    """The same at stride 1040, the store loop's wave-uniform form with 65 chunks per slot: one workgroup per CU,
+    (512 + 19) x CUs datagrams, so every workgroup stages a second batch whose first ring chunk is not 0 and whose
+    64-chunk rounds cross datagram boundaries; full slots, 1000-byte datagrams and short last ones."""
+    import launch_depths as L
+    from ctstraffic_amd import Engine
+
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    total = L.batched_n("ring1040", cus)
+    depth = L.batch_fill_depth(total, L.RING_BATCH, cus, 1, 1040)
+    assert L.batched_reaches("ring1040", depth) == [], depth
+    ks = [1, 511, 77, 1025, 2, 3 * 512]
+    ks.append(total - sum(ks) - 9)
+    ks += [9]
+    sizes = [1040, 1040, 1000, 1040, 1040, 1000, 1040, 1040]
+    settings = [(m * k - (0 if c % 2 else 20), m, 2) for c, (k, m) in enumerate(zip(ks, sizes))]
+    assert sum(-(-F // m) for F, m, _ in settings) == total
+    old = os.environ.get("CTS_RING_FILL_BLOCKS_PER_CU")
+    os.environ["CTS_RING_FILL_BLOCKS_PER_CU"] = "1"
+    try:
+        eng = Engine(0)
+    finally:
+        if old is None:
+            del os.environ["CTS_RING_FILL_BLOCKS_PER_CU"]
+        else:
+            os.environ["CTS_RING_FILL_BLOCKS_PER_CU"] = old
+    try:
+        table, view = _pair(eng, settings, 1040, total)
+        _tick(table, view, range(len(ks)), where="one workgroup per CU, stride 1040")
+        assert view.tick["datagrams"] == total
+    finally:
+        eng.close()
+
+
 # ---- 7: argument edges -----------------------------------------------------------------------------------------
 def test_argument_edges(engine):
     settings = [(3000, 1400, 3), (100, 60, 3)]
