@@ -5,7 +5,9 @@
 #                      and the tests run
 #                      (tools/libcts_bench_multi.so, tools/pattern_cpu_probe)
 #   make probes     -> the measurement probes of tools/ (ceilings, timelines, ablations; built before an A/B call)
-#   make asm        -> ctstraffic_amd/build/cts_kernels-gfx950.s, cts_accounting-gfx950.s (disassembly for inspection)
+#   make asm        -> ctstraffic_amd/build/<unit>-gfx950.s for every kernel unit: cts_verify, cts_media_stream_recv,
+#                      cts_fill, cts_accounting (disassembly for inspection; tools/kernel_text.py lists and compares
+#                      the kernels in them)
 HIPCC     ?= /opt/rocm/bin/hipcc
 ARCH      ?= gfx950
 HIPFLAGS  ?= -O3 -std=c++17 -fPIC -Wall -Wno-unused-result --offload-arch=$(ARCH) -Iinclude -Ictstraffic_amd/csrc
@@ -57,14 +59,14 @@ tools/%: tools/%.hip
 	$(HIPCC) --offload-arch=$(ARCH) -O3 $< -o $@
 
 # the product fill kernel included verbatim (diagnostic)
-tools/fill_bisect: tools/fill_bisect.hip $(CSRC)/cts_kernels.hip $(HDRS)
+tools/fill_bisect: tools/fill_bisect.hip $(CSRC)/cts_fill.hip $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -Iinclude -I$(CSRC) $< -o $@
 
 # the product verify kernel beside a plain read of the same shape: times and per-workgroup timelines (diagnostic);
 # the _kp build preloads the kernel arguments into SGPRs
-tools/verify_timeline: tools/verify_timeline.hip $(CSRC)/cts_kernels.hip $(HDRS)
+tools/verify_timeline: tools/verify_timeline.hip $(CSRC)/cts_verify.hip $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -Iinclude -I$(CSRC) $< -o $@
-tools/verify_timeline_kp: tools/verify_timeline.hip $(CSRC)/cts_kernels.hip $(HDRS)
+tools/verify_timeline_kp: tools/verify_timeline.hip $(CSRC)/cts_verify.hip $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -Iinclude -I$(CSRC) -DCTS_TOOL_KERNARG_PRELOAD=1 \
 	  -mllvm -amdgpu-kernarg-preload-count=16 $< -o $@
 
@@ -77,23 +79,23 @@ tools/verify_timeline_r05: tools/verify_timeline.hip ctstraffic_amd/build/cts_ke
 	  '-DCTS_KERNELS_FILE="../ctstraffic_amd/build/cts_kernels_r05.hip"' $< -o $@
 
 # a slim one-buffer-per-workgroup verify beside the product and the plain slab read (diagnostic, profiles/r05/d/)
-tools/slab_verify_probe: tools/slab_verify_probe.hip $(CSRC)/cts_kernels.hip $(HDRS)
+tools/slab_verify_probe: tools/slab_verify_probe.hip $(CSRC)/cts_verify.hip $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -Iinclude -I$(CSRC) -mllvm -amdgpu-kernarg-preload-count=16 $< -o $@
 
 # the HBM write ceiling on a rotated 4 GiB footprint beside the product fill kernel (diagnostic, profiles/r06/)
-tools/write_ceiling_rot: tools/write_ceiling_rot.hip $(CSRC)/cts_kernels.hip $(HDRS)
+tools/write_ceiling_rot: tools/write_ceiling_rot.hip $(CSRC)/cts_fill.hip $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -Iinclude -I$(CSRC) $< -o $@
 
 # the MediaStream ring fill in piece order beside the product's (diagnostic, profiles/r06/g/)
-tools/ring_order_probe: tools/ring_order_probe.hip $(CSRC)/cts_kernels.hip $(HDRS)
+tools/ring_order_probe: tools/ring_order_probe.hip $(CSRC)/cts_fill.hip $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -Iinclude -I$(CSRC) $< -o $@
 
 # the product MediaStream fill beside flat ring walks (diagnostic)
-tools/ring_fill_probe: tools/ring_fill_probe.hip $(CSRC)/cts_kernels.hip $(HDRS)
+tools/ring_fill_probe: tools/ring_fill_probe.hip $(CSRC)/cts_fill.hip $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -Iinclude -I$(CSRC) $< -o $@
 
 # the product mailbox kernel driven by a bare host loop (diagnostic)
-tools/mailbox_bisect: tools/mailbox_bisect.hip $(CSRC)/cts_kernels.hip $(HDRS)
+tools/mailbox_bisect: tools/mailbox_bisect.hip $(CSRC)/cts_verify.hip $(HDRS)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -Iinclude -I$(CSRC) $< -o $@
 
 # cts_fill through the C ABI without PyTorch (diagnostic)

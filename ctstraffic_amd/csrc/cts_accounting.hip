@@ -3,7 +3,8 @@
 //   conn_accumulate      the same pass keeping each connection's entry too; conn_close, conn_slots_rebase
 //   ms_conn_accumulate   the MediaStream connections' pass over descriptors and statuses; ms_conn_render, ms_conn_close
 // conn_accumulate sums what shares a connection's entry with walk_runs; ms_conn_accumulate still has that walk written
-// out (see there). The receive pass that lowers the DataError slots (ms_verify_status_ordinal) is in cts_kernels.hip.
+// out (see there). The receive pass that lowers the DataError slots (ms_verify_status_ordinal) is in
+// cts_media_stream_recv.hip.
 #include <hip/hip_runtime.h>
 
 #include "cts_device_util.hpp"

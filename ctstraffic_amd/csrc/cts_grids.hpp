@@ -2,7 +2,8 @@
 // no device code).
 //
 // Every rule takes plain integers: the launch's item count, the device's compute units and the blocks-per-CU cap of
-// its path (LaunchGeometry's values, cts_internal.hpp). The launchers of cts_kernels.hip call them; how deep a
+// its path (LaunchGeometry's values, cts_internal.hpp; cts_launch.hpp's wrappers pick them). The launchers of
+// cts_verify.hip, cts_media_stream_recv.hip and cts_fill.hip call them; how deep a
 // kernel's outer loop runs (batches per workgroup, rounds per wave, ring flushes) follows from the grid alone.
 // tests/cpp/grids_check.cpp prints the rules' answers; tests/launch_depths.py states the same arithmetic in Python
 // with the loop depths on top, and tests/test_launch_depths_cpu.py holds the two together.

@@ -1,4 +1,4 @@
-// cts_internal.hpp — launchers shared between the kernel TU and the C-ABI TU.
+// cts_internal.hpp — launchers shared between the kernel units (the .hip files) and the C-ABI files.
 #pragma once
 
 #include <hip/hip_runtime_api.h>

@@ -1,5 +1,5 @@
 // cts_ring_store_loop.hpp — the store loop of one staged batch of a datagram ring. A fragment, not a header: it is
-// included inside the batch loop of media_stream_fill_ring_kernel and of ms_server_fill (cts_kernels.hip), so
+// included inside the batch loop of media_stream_fill_ring_kernel and of ms_server_fill (cts_fill.hip), so
 // that both kernels run one loop and the compiler sees, in each of them, the text it saw before the second one
 // existed (a function taking the LDS arrays changed the first kernel's instructions).
 //

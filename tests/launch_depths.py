@@ -5,7 +5,8 @@ the loop's second pass on: a prefetched descriptor, a refilled LDS stage, an out
 restates the launchers' grid rules (ctstraffic_amd/csrc/cts_grids.hpp; the CPU test holds the two together through
 tests/cpp/grids_check.cpp) and, on top of them, how deep each kernel's loop runs for a given launch, so a test can
 assert that its shape reaches the later passes before it compares a device result. The depth functions follow the
-kernels of ctstraffic_amd/csrc/cts_kernels.hip line by line; each names the loop it models.
+kernels of ctstraffic_amd/csrc/cts_verify.hip, cts_media_stream_recv.hip and cts_fill.hip line by line; each names the
+loop it models.
 """
 import numpy as np
 

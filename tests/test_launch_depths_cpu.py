@@ -1,7 +1,7 @@
 """CPU: what tests/test_loop_depth_gpu.py rests on (tests/launch_depths.py).
 
 1. The model's grid rules are the launchers': tests/cpp/grids_check.cpp, built here with g++ over
-   ctstraffic_amd/csrc/cts_grids.hpp (the header the launchers of cts_kernels.hip call), prints the same numbers, at,
+   ctstraffic_amd/csrc/cts_grids.hpp (the header the launchers of the kernel units call), prints the same numbers, at,
    one below and one above every cap, for 64, 104, 228, 256 and 304 compute units.
 2. Every shape of the loop-depth tests reaches its depth facts at each of those CU counts, and the depth functions
    agree with plain one-item-at-a-time loops on a small device.

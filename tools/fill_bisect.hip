@@ -1,8 +1,8 @@
-// fill_bisect.hip — the product fill kernel (cts_kernels.hip, included verbatim) launched directly, on
+// fill_bisect.hip — the product fill kernel (cts_fill.hip, included verbatim) launched directly, on
 // one arena written over and over and on 4 arenas rotated per launch (1 GiB: more than the 256 MB MALL
 // can keep). Rewriting one 256 MiB arena runs from the MALL and reads as 6.9 TB/s; rotated, the same
 // kernel writes HBM at the rate cts_fill shows in bench.py. Diagnostic only.
-#include "../ctstraffic_amd/csrc/cts_kernels.hip"
+#include "../ctstraffic_amd/csrc/cts_fill.hip"
 
 #include <cstdio>
 #include <vector>

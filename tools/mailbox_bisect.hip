@@ -1,11 +1,11 @@
-// mailbox_bisect.hip — the product mailbox kernel (cts_kernels.hip, included verbatim) driven by a bare
+// mailbox_bisect.hip — the product mailbox kernel (cts_verify.hip, included verbatim) driven by a bare
 // host loop: no engine, no mutex, no ticket bookkeeping. Per 64 KiB verify it reports the mean time from
 // writing the job to the first and to the last of the group's part records, so the gap between
 // tools/sync_probe (cts_verify_mapped) and tools/mailbox_probe's ping-pong splits into host overhead,
 // the kernel's own work, and the spread of the 16 workgroups' poll phases. Diagnostic only.
 //   build: make tools/mailbox_bisect     run: tools/mailbox_bisect [iters]
 #define CTS_MAILBOX_TRACE 1
-#include "../ctstraffic_amd/csrc/cts_kernels.hip"
+#include "../ctstraffic_amd/csrc/cts_verify.hip"
 
 #include <algorithm>
 #include <vector>

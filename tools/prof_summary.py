@@ -72,7 +72,7 @@ def _kname(name):
     base = name.split("(")[0].split("<")[0].split("::")[-1].strip()
     if base in ("media_stream_verify_quad_kernel", "verify_quad_kernel") and "<" in name:
         targs = [t.strip() for t in name.split("(")[0].split("<", 1)[1].rsplit(">", 1)[0].split(",")]
-        # template arguments <NT, STRIDED[, RING, STATUS, FRAMES]> (cts_kernels.hip)
+        # template arguments <NT, STRIDED[, RING, STATUS, FRAMES]> (cts_verify.hip, cts_media_stream_recv.hip)
         tag = "[strided]" if len(targs) > 1 and targs[1] == "true" else ""
         if base == "media_stream_verify_quad_kernel" and len(targs) > 3 and targs[3] == "true":
             tag += "[status]"

@@ -8,7 +8,7 @@
 // nontemporal and plain stores. One JSON line per (case, round). Diagnostic only.
 //   build: make tools/ring_fill_probe     run: tools/ring_fill_probe [datagrams] [rounds]
 #define CTS_TUNING 1  // the round-3 wave-per-buffer fills too
-#include "../ctstraffic_amd/csrc/cts_kernels.hip"
+#include "../ctstraffic_amd/csrc/cts_fill.hip"
 
 #include <cstdio>
 #include <cstdlib>

@@ -1,5 +1,5 @@
 // ring_order_probe.hip — the MediaStream ring fill (cts_media_stream_fill_strided) in piece order, beside the product
-// kernel (cts_kernels.hip, included verbatim). Diagnostic only (profiles/r06/g/).
+// kernel (cts_fill.hip, included verbatim). Diagnostic only (profiles/r06/g/).
 //
 // The ring is cut into 8 KiB pieces of its 16-byte chunks, dealt round robin to the workgroups (as fill_pieces_kernel
 // deals the pieces of 64 KiB buffers), so the grid's concurrent stores cover adjacent pieces. A batch of 16 pieces'
@@ -8,7 +8,7 @@
 // A second form (ring_wave_pieces_kernel, profiles/r06/q/) deals 2 KiB pieces to every wave, without LDS or barriers.
 // Every datagram's bytes are compared with the product's output; 16 M x 1472 B with 1 % of the lengths random.
 //   build: make tools/ring_order_probe     run: tools/ring_order_probe [datagrams] [reps]
-#include "../ctstraffic_amd/csrc/cts_kernels.hip"
+#include "../ctstraffic_amd/csrc/cts_fill.hip"
 
 #include <cstdio>
 #include <cstdlib>

@@ -15,7 +15,7 @@
 //   build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Ictstraffic_amd/csrc
 //          -mllvm -amdgpu-kernarg-preload-count=16 tools/slab_verify_probe.hip -o tools/slab_verify_probe
 //   run:   tools/slab_verify_probe [passes] [launches]
-#include "../ctstraffic_amd/csrc/cts_kernels.hip"
+#include "../ctstraffic_amd/csrc/cts_verify.hip"
 
 #include <cstdio>
 #include <cstdlib>

@@ -1,7 +1,7 @@
 // verify_timeline.hip — where does a config-2 verify launch spend the time a plain streaming read of the same
 // bytes does not? (DESIGN.md §3 "Where a 256 MiB launch's last few percent go"; VERDICT r03 "Next round" 3.)
 //
-// The product kernel (cts_kernels.hip, included verbatim) against the plain read of the same shape, in one process on
+// The product kernel (cts_verify.hip, included verbatim) against the plain read of the same shape, in one process on
 // one box, 8 rotated 256 MiB arenas (4096 x 64 KiB buffers each; 75 % phase-0 / 25 % random expected offsets, one
 // corrupt byte per 1024 buffers, as bench.py's config 2):
 //   time    : HIP events around R launches, per launch: the product verify_wg_kernel ("product_verify_us"), a
@@ -18,7 +18,7 @@
 #ifdef CTS_KERNELS_FILE
 #include CTS_KERNELS_FILE
 #else
-#include "../ctstraffic_amd/csrc/cts_kernels.hip"
+#include "../ctstraffic_amd/csrc/cts_verify.hip"
 #endif
 #ifndef CTS_TL_COUNTERS
 #define CTS_TL_COUNTERS cts::kCounterCount

@@ -8,7 +8,7 @@
 //                  8 waves per CU = 2 workgroups of 256 per CU; also at 4 and 16 waves per CU
 //   dword_flat   : the same stores, grid-strided over the arena (consecutive waves on adjacent 256 B)
 //   b16_slab     : 16 B per lane (1 KiB per wave-instruction), whole 64 KiB slabs, 4/8/16 waves per CU
-//   product_fill : cts::fill_kernel<256> (cts_kernels.hip, included verbatim) on config 2's 4096 descriptors, at
+//   product_fill : cts::fill_kernel<256> (cts_fill.hip, included verbatim) on config 2's 4096 descriptors, at
 //                  the product's grid (1 workgroup of 4 waves per CU) and at 2 and 4 per CU
 //   b16_flat     : 16-B stores grid-strided (second pass)
 //   fill_pieces  : the candidate fill order, buffers cut in 4/8/16 KiB pieces dealt round robin (second pass)
@@ -16,7 +16,7 @@
 //                  every 1-8 pieces or never (profiles/r06/l/)
 // Each (shape, waves) is timed over 32 launches (HIP events), the whole sweep three times, interleaved; one JSON
 // line per measurement. Diagnostic only (profiles/r06/a/write_ceiling_rotated.jsonl: SWEEP=0; SWEEP=1 the second).
-#include "../ctstraffic_amd/csrc/cts_kernels.hip"
+#include "../ctstraffic_amd/csrc/cts_fill.hip"
 
 #include <cstdio>
 #include <cstdlib>

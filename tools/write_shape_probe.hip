@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(256) write_slab_kernel(uint8_t* __restrict__ p
     }
 }
 
-// a copy of cts_kernels.hip's whole-span fill round (fill_whole_rounds, even phase): the expected words
+// a copy of cts_fill.hip's whole-span fill round (fill_whole_rounds, even phase): the expected words
 // stepped from a packed u16-pair base with an opaque-register barrier, global stores for full rounds
 template <int U, bool BARRIER>
 __device__ __forceinline__ u32x4 fill_step(uint32_t B, int u)
