@@ -136,6 +136,21 @@ class CtsCountersUdp(ctypes.Structure):
         return {f: int(getattr(self, f)) for f, _ in self._fields_}
 
 
+class CtsCountersSent(ctypes.Structure):
+    """cts_counters_sent: what the TCP senders' ticks add to a counter block (laid out like cts_counters_ex)."""
+    _fields_ = [
+        ("bytes_sent", ctypes.c_uint64),
+        ("buffers_sent", ctypes.c_uint64),
+        ("connections_finished", ctypes.c_uint64),
+        ("reserved0", ctypes.c_uint64),
+        ("reserved1", ctypes.c_uint64),
+        ("reserved2", ctypes.c_uint64),
+    ]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
 class CtsAllreduceSetup(ctypes.Structure):
     """cts_allreduce_setup: where the newest RCCL clique's set-up time went (ms)."""
     _fields_ = [
@@ -227,6 +242,15 @@ def _declare(L: ctypes.CDLL) -> None:
         "cts_media_stream_servers_scratch_bytes": ([u32], ctypes.c_size_t),
         "cts_media_stream_servers_send": ([P, P, u64, u32, u64, u32, P, u32, P, u32, ctypes.c_int64, ctypes.c_int64,
                                            P, P, P, P, P, P, ctypes.c_size_t, P], i32),
+        "cts_tcp_sender_init": ([u64, u32, P], i32),
+        "cts_tcp_senders_scratch_bytes": ([u32], ctypes.c_size_t),
+        "cts_tcp_senders_send": ([P, P, u64, u32, u64, u32, P, u32, u32, P, u32, P, P, P, P, P, ctypes.c_size_t, P],
+                                 i32),
+        "cts_counters_read_sent": ([P, P, ctypes.POINTER(CtsCountersSent), P], i32),
+        "cts_counters_read_multi_sent": ([ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), u32,
+                                          ctypes.POINTER(CtsCountersSent)], i32),
+        "cts_counters_allreduce_sent": ([ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), u32,
+                                         ctypes.POINTER(CtsCountersSent)], i32),
         "cts_counters_device_bytes": ([], ctypes.c_size_t),
         "cts_counters_reset": ([P, P, P], i32),
         "cts_counters_read": ([P, P, ctypes.POINTER(CtsCounters), P], i32),

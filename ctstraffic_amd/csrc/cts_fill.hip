@@ -5,6 +5,9 @@
 //   ms_server_sums / _scan / _apply, ms_server_fill   the MediaStream servers' tick: slots planned by a prefix sum over
 //                                     the listed connections, then the ring fill with media_stream_fill_ring_kernel's
 //                                     store loop (cts_ring_store_loop.hpp) and no per-datagram metadata
+//   tcp_sender_sums / _apply / _descs, tcp_sender_fill_pieces / _small   the TCP senders' tick: the same planning, a
+//                                     descriptor per written slot, then fill_pieces_kernel's or fill_kernel's loop
+//                                     (cts_fill_pieces_loop.hpp, cts_fill_team_loop.hpp) over a count read on the device
 // The expected chunk is regenerated in registers as in the verify (cts_chunks.hpp); the verify kernels are in
 // cts_verify.hip, the MediaStream receive in cts_media_stream_recv.hip. The alternatives that lost are in DESIGN.md §10.
 #include <hip/hip_runtime.h>
@@ -123,21 +126,7 @@ template <int TEAM, bool NTS = false>
 __global__ void __launch_bounds__(kBlock) fill_kernel(uint8_t* __restrict__ arena, uint64_t arena_bytes,
                                                       const cts_buf_desc* __restrict__ descs, uint32_t n)
 {
-    constexpr int TEAMS = kBlock / TEAM;
-    constexpr int FU = TEAM == kBlock ? 4 : 2;  // stores per lane per whole-span round
-    const uint32_t lane = threadIdx.x % TEAM;
-    const uint32_t team = (TEAM == kBlock) ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x / TEAM);
-    const uint32_t step = gridDim.x * TEAMS;
-    uint32_t i = blockIdx.x * TEAMS + team;
-    // the next buffer's descriptor is loaded while this one's stores go out: with one workgroup per CU
-    // nothing else hides a dependent descriptor load per buffer (49.4 -> see DESIGN §3 fill)
-    cts_buf_desc dn;
-    if (i < n) dn = descs[i];
-    for (; i < n; i = (uint64_t)i + step < n ? i + step : n) {
-        const cts_buf_desc d = dn;
-        if ((uint64_t)i + step < n) dn = descs[i + step];
-        fill_one<TEAM, FU, NTS>(arena, arena_bytes, d, lane);
-    }
+#include "cts_fill_team_loop.hpp"
 }
 
 // The workgroup path's fill in piece order. Every buffer is cut into ppb pieces of kFillPiece bytes (the last
@@ -195,57 +184,7 @@ __global__ void __launch_bounds__(kBlock) fill_pieces_kernel(uint8_t* __restrict
                                                              const cts_buf_desc* __restrict__ descs, uint32_t n,
                                                              uint32_t ppb)
 {
-    typedef u32x4 __attribute__((address_space(1)))* gstore_ptr;
-    constexpr uint32_t kChunks = PIECE / 16;
-    static_assert(PIECE % (16 * kBlock) == 0 && BATCH <= 64, "whole rounds per piece; one lane per piece");
-    const uint64_t total = (uint64_t)n * ppb;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t m_own = lane & 63u;  // every wave decodes the batch for itself (readlane reads the own wave)
-    const uint64_t G = gridDim.x;
-    PieceJob cur = decode_piece<PIECE>(arena, arena_bytes, descs, blockIdx.x + (uint64_t)m_own * G, total, ppb,
-                                       m_own < (uint32_t)BATCH);
-    for (uint64_t v0 = blockIdx.x; v0 < total; v0 += (uint64_t)BATCH * G) {
-        // the next batch, decoded before this batch's stores. Its load is waited for at once, which also waits for
-        // the previous batch's stores (vector loads and stores share one in-order counter): once per batch, the wave
-        // cadence that keeps the grid's stores adjacent (no wait 5.6 TB/s, a wait every 1-4 pieces 5.1-6.2, the
-        // decode after the stores 5.7, against 6.2 here: profiles/r06/j, l)
-        const PieceJob nxt = decode_piece<PIECE>(arena, arena_bytes, descs, v0 + (uint64_t)(BATCH + m_own) * G, total,
-                                                 ppb, m_own < (uint32_t)BATCH);
-#pragma unroll 1
-        for (int m = 0; m < BATCH; ++m) {
-            const uint32_t kind = lane_u32(cur.kind, m);
-            if (kind == 0u) continue;
-            const uint64_t base = ((uint64_t)lane_u32((uint32_t)(cur.base >> 32), m) << 32) | lane_u32((uint32_t)cur.base, m);
-            const uint32_t q0 = lane_u32(cur.q0, m), cb = lane_u32(cur.cb, m), ce = lane_u32(cur.ce, m);
-            if (kind == 1u) {  // whole 16-byte chunks: straight stores
-                const gstore_ptr g = (gstore_ptr)base;
-                const uint32_t sh = q0 & 1u;
-                if (ce <= cb + kChunks) {  // one piece: kChunks / kBlock stores per lane, unrolled
-#pragma unroll
-                    for (uint32_t u = 0; u < kChunks / kBlock; ++u) {
-                        const uint32_t c = cb + u * kBlock + lane;
-                        if (c < ce) {
-                            const u32x4 e = expected_chunk((q0 + 16u * c) & 0xFFFFu, sh);
-                            if constexpr (NTS) __builtin_nontemporal_store(e, g + c);
-                            else g[c] = e;
-                        }
-                    }
-                } else {  // the last piece of a buffer longer than the hint said
-                    for (uint32_t c = cb + lane; c < ce; c += kBlock) {
-                        const u32x4 e = expected_chunk((q0 + 16u * c) & 0xFFFFu, sh);
-                        if constexpr (NTS) __builtin_nontemporal_store(e, g + c);
-                        else g[c] = e;
-                    }
-                }
-            } else {  // the edge chunks write only their own bytes
-                const uint32_t nchunks = lane_u32(cur.nchunks, m), lo = lane_u32(cur.lo, m),
-                               hi_last = lane_u32(cur.hi_last, m);
-                u32x4* p = reinterpret_cast<u32x4*>((uintptr_t)base);
-                for (uint32_t c = cb + lane; c < ce; c += kBlock) fill_chunk<NTS>(p, c, nchunks, q0, lo, hi_last);
-            }
-        }
-        cur = nxt;
-    }
+#include "cts_fill_pieces_loop.hpp"
 }
 
 // One long span, all workgroups cooperating (sender buffer materialisation).
@@ -727,6 +666,201 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // ---------------------------------------------------------------------------------------------
+// TCP senders on the device (cts_tcp_senders_send): one tick of the listed connections' buffer sends with no host
+// descriptor per buffer. Listed connection i wants w_i = min(max_buffers, ceil(R / B)) slots (0 when it sends nothing
+// whatever the room); p_i, the exclusive prefix of the wants in listed order, is its first slot, and it takes
+// t_i = min(w_i, capacity - min(p_i, capacity)) of them. The planning is the servers' three-launch scheme in tiles of
+// kMsServerTile (tcp_sender_sums, ms_server_scan as it stands, tcp_sender_apply); apply also leaves every listed
+// connection's bytes_sent from before the move in the scratch. tcp_sender_descs then writes one descriptor per
+// written slot, and the fill runs over those descriptors with the existing loops (cts_fill_pieces_loop.hpp,
+// cts_fill_team_loop.hpp), its buffer count read from the tick block.
+// Scratch (TcpSenderScratch, cts_internal.hpp): u64 prefix[n + 1], u64 sums[tiles], u64 before[n], a tick.
+static_assert(sizeof(cts_tcp_sender_tick) == sizeof(cts_ms_server_tick), "ms_server_scan zeroes either tick block");
+
+// The slots listed connection c wants, and its code when it sends nothing whatever the room.
+__device__ __forceinline__ uint64_t tcp_sender_want(const cts_tcp_sender_state* __restrict__ senders, uint32_t c,
+                                                    uint32_t n_conns, uint32_t stride, uint32_t max_buffers,
+                                                    uint32_t& code)
+{
+    code = CTS_TCP_SENDER_SKIPPED;
+    if (c >= n_conns) return 0u;
+    const uint32_t B = senders[c].buffer_size;
+    if (B == 0u || B > stride) return 0u;
+    code = CTS_TCP_SENDER_ENDED;
+    const uint64_t sent = senders[c].bytes_sent, transfer = senders[c].transfer_bytes;
+    if (senders[c].finished != 0u || sent >= transfer) return 0u;
+    code = CTS_TCP_SENDER_SENT;
+    const uint64_t R = transfer - sent;
+    const uint64_t k = R / B + (R % B != 0u ? 1u : 0u);
+    return k < max_buffers ? k : max_buffers;
+}
+
+// A wave's 64-bit sum from four 16-bit limbs summed in 32 bits. (Not wave_sum64: with it used here as well,
+// ms_server_sums and ms_server_apply compiled to other instruction text, one 64-bit add's operands swapped)
+__device__ __forceinline__ uint64_t tcp_wave_sum64(uint64_t v)
+{
+    uint64_t s = 0;
+#pragma unroll
+    for (int l = 0; l < 4; ++l) s += (uint64_t)wave_sum((uint32_t)(v >> (16 * l)) & 0xFFFFu) << (16 * l);
+    return s;
+}
+
+__global__ void __launch_bounds__(kBlock)
+    tcp_sender_sums(const uint32_t* __restrict__ ids, uint32_t n, const cts_tcp_sender_state* __restrict__ senders,
+                    uint32_t n_conns, uint32_t stride, uint32_t max_buffers, uint64_t* __restrict__ sums)
+{
+    __shared__ uint64_t wsum[kBlock / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * kMsServerTile + threadIdx.x;
+    uint32_t code;
+    const uint64_t want = i < n ? tcp_sender_want(senders, ids[i], n_conns, stride, max_buffers, code) : 0u;
+    const uint64_t s = tcp_wave_sum64(want);
+    if ((threadIdx.x & 63u) == 0u) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint64_t t = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) t += wsum[w];
+        sums[blockIdx.x] = t;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock)
+    tcp_sender_apply(const uint32_t* __restrict__ ids, uint32_t n, cts_tcp_sender_state* __restrict__ senders,
+                     uint32_t n_conns, uint32_t stride, uint32_t capacity, uint32_t max_buffers,
+                     const uint64_t* __restrict__ sums, uint64_t* __restrict__ prefix, uint64_t* __restrict__ before,
+                     uint32_t* __restrict__ codes, cts_tcp_sender_tick* __restrict__ tick, uint64_t* __restrict__ sent_block)
+{
+    __shared__ uint64_t wsum[kBlock / 64];
+    __shared__ uint64_t ctr[kBlock / 64][kCounterCount];
+    __shared__ uint32_t red[kBlock / 64][5];
+    zero_counters<kBlock / 64>(ctr);
+    const uint64_t i = (uint64_t)blockIdx.x * kMsServerTile + threadIdx.x;
+    uint32_t code = CTS_TCP_SENDER_SENT, c = 0u;
+    uint64_t want = 0;
+    if (i < n) {
+        c = ids[i];
+        want = tcp_sender_want(senders, c, n_conns, stride, max_buffers, code);
+    }
+    uint64_t total;
+    const uint64_t p = sums[blockIdx.x] + tile_scan_exclusive(want, wsum, total);
+    uint64_t bytes = 0;
+    uint32_t buffers = 0, sent = 0, finished = 0, no_room = 0, skipped = 0;
+    if (i < n) {
+        prefix[i] = p;
+        const uint64_t pc = p < (uint64_t)capacity ? p : (uint64_t)capacity;
+        const uint64_t t = want < (uint64_t)capacity - pc ? want : (uint64_t)capacity - pc;
+        uint64_t was = 0;
+        if (code != CTS_TCP_SENDER_SENT) {
+            skipped = 1u;
+        } else if (t == 0u) {
+            no_room = 1u;
+            code = CTS_TCP_SENDER_NO_ROOM;
+        } else {
+            // the only step that knows how many slots the connection takes is the one that moves its entry
+            cts_tcp_sender_state* e = senders + c;
+            was = e->bytes_sent;
+            const uint64_t R = e->transfer_bytes - was, full = t * e->buffer_size;  // t <= capacity < 2^32
+            bytes = full < R ? full : R;
+            buffers = (uint32_t)t;
+            sent = 1u;
+            e->bytes_sent = was + bytes;
+            e->buffers_sent += t;
+            if (bytes == R) {
+                e->finished = 1u;
+                finished = 1u;
+                code = CTS_TCP_SENDER_FINISHED;
+            }
+        }
+        before[i] = was;
+        if (codes != nullptr) codes[i] = code;
+    }
+    const uint64_t own_bytes = tcp_wave_sum64(bytes);
+    buffers = wave_sum(buffers);
+    sent = wave_sum(sent);
+    finished = wave_sum(finished);
+    no_room = wave_sum(no_room);
+    skipped = wave_sum(skipped);
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0u) {
+        ctr[wave][0] = own_bytes;  // cts_counters_sent.bytes_sent (TcpStatusDetails.m_bytesSent, ctsIOPattern.cpp:510)
+        ctr[wave][1] = buffers;    // .buffers_sent
+        ctr[wave][2] = finished;   // .connections_finished
+        red[wave][0] = buffers;
+        red[wave][1] = sent;
+        red[wave][2] = finished;
+        red[wave][3] = no_room;
+        red[wave][4] = skipped;
+    }
+    flush_counters<kBlock / 64>(sent_block, ctr);  // barrier first
+    if (threadIdx.x < 5u) {
+        uint32_t s = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) s += red[w][threadIdx.x];
+        uint32_t* const words = &tick->buffers;  // buffers, connections_sent, _finished, _no_room, _skipped
+        if (s) atomicAdd(words + threadIdx.x, s);
+    } else if (threadIdx.x == 5u) {
+        uint64_t s = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) s += ctr[w][0];
+        if (s) atomicAdd((unsigned long long*)&tick->bytes, (unsigned long long)s);
+    }
+}
+
+// One lane per tick-local slot g < total, grid-stride over the capacity: the descriptor of buffer j = g - prefix[i] of
+// listed connection i, the last one with prefix[i] <= g (prefix[] stays in L2). A launch of its own: at the fill's one
+// workgroup per CU nothing hides a chain of dependent loads in the piece decode, and a thread per connection writing
+// its t descriptors would serialise a one-connection tick.
+__global__ void __launch_bounds__(kBlock)
+    tcp_sender_descs(uint32_t stride, uint64_t first_slot, uint32_t capacity, const uint32_t* __restrict__ ids,
+                     uint32_t n, const cts_tcp_sender_state* __restrict__ senders, uint32_t n_conns,
+                     const uint64_t* __restrict__ prefix, const uint64_t* __restrict__ before,
+                     const cts_tcp_sender_tick* __restrict__ tick, cts_buf_desc* __restrict__ descs)
+{
+    // (the clamps only matter to a caller who lists a connection twice: nothing is written outside the capacity or
+    // read outside the table then either, and no descriptor is longer than its slot)
+    const uint32_t total = tick->buffers < capacity ? tick->buffers : capacity;
+    for (uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x; g < total; g += (uint64_t)gridDim.x * kBlock) {
+        const uint64_t i = ms_server_listed(prefix, 0u, n, g);
+        const uint64_t j = g - prefix[i];
+        const uint32_t c = ids[i];
+        uint32_t len = 0u, off = 0u;
+        if (c < n_conns) {
+            const uint32_t B = senders[c].buffer_size;
+            const uint64_t was = before[i], start = was + j * B;  // j < capacity: the product stays in 64 bits
+            const uint64_t end = senders[c].transfer_bytes;
+            const uint64_t left = start < end ? end - start : 0u;
+            len = left < (uint64_t)B ? (uint32_t)left : B;
+            if (len > stride) len = 0u;
+            off = (uint32_t)(start & 0xFFFFu);
+        }
+        descs[g] = cts_buf_desc{(first_slot + g) * stride, len, off, c, 0u};
+    }
+}
+
+// The fill over the tick's descriptors: the existing loops, their buffer count read from the tick block (the grid
+// comes from the capacity; workgroups past the count find nothing to do).
+template <bool NTS>
+__global__ void __launch_bounds__(kBlock)
+    tcp_sender_fill_pieces(uint8_t* __restrict__ arena, uint64_t arena_bytes, const cts_buf_desc* __restrict__ descs,
+                           const cts_tcp_sender_tick* __restrict__ tick, uint32_t capacity, uint32_t ppb)
+{
+    constexpr uint32_t PIECE = kFillPiece;
+    constexpr int BATCH = kPieceBatch;
+    const uint32_t n = tick->buffers < capacity ? tick->buffers : capacity;
+#include "cts_fill_pieces_loop.hpp"
+}
+
+template <bool NTS>
+__global__ void __launch_bounds__(kBlock)
+    tcp_sender_fill_small(uint8_t* __restrict__ arena, uint64_t arena_bytes, const cts_buf_desc* __restrict__ descs,
+                          const cts_tcp_sender_tick* __restrict__ tick, uint32_t capacity)
+{
+    constexpr int TEAM = 64;
+    const uint32_t n = tick->buffers < capacity ? tick->buffers : capacity;
+#include "cts_fill_team_loop.hpp"
+}
+
+// ---------------------------------------------------------------------------------------------
 static_assert(kGridBlock == (uint32_t)kBlock && kGridFillPiece == kFillPiece && kGridFillBatch == kFillBatch &&
                   kGridRingBatch == kRingBatch,
               "cts_grids.hpp sizes the launches of these kernels");
@@ -832,6 +966,61 @@ hipError_t launch_ms_server_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t 
                 descs, lengths, full_slots, capacity, n_conns);
         },
         geo.fill_nt != 0, stride >= 1024u);
+    return hipGetLastError();
+}
+
+// cts_tcp_senders_send's planning: three launches, the middle one the servers' single-workgroup scan
+hipError_t launch_tcp_sender_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
+                                  cts_tcp_sender_state* senders, uint32_t n_conns, uint32_t stride, uint32_t capacity,
+                                  uint32_t* codes, cts_tcp_sender_tick* tick, uint64_t* sent_counters,
+                                  const TcpSenderScratch& scratch, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    const uint64_t tiles = ms_server_tiles(n);
+    tcp_sender_sums<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, senders, n_conns, stride, max_buffers,
+                                                            scratch.sums);
+    ms_server_scan<<<1, kBlock, 0, stream>>>(scratch.sums, tiles, scratch.prefix + n,
+                                             reinterpret_cast<uint32_t*>(tick));
+    tcp_sender_apply<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, senders, n_conns, stride, capacity,
+                                                             max_buffers, scratch.sums, scratch.prefix, scratch.before,
+                                                             codes, tick, sent_counters);
+    return hipGetLastError();
+}
+
+// the tick's descriptors: one lane per slot of the capacity, at most the verify path's grid (the total is on the device)
+hipError_t launch_tcp_sender_descs(uint32_t stride, uint64_t first_slot, uint32_t capacity, const uint32_t* conn_ids,
+                                   uint32_t n, const cts_tcp_sender_state* senders, uint32_t n_conns,
+                                   const TcpSenderScratch& scratch, const cts_tcp_sender_tick* tick,
+                                   cts_buf_desc* descs, hipStream_t stream, const LaunchGeometry& geo)
+{
+    if (n == 0 || capacity == 0) return hipSuccess;
+    const uint32_t grid = grid_for((uint32_t)(((uint64_t)capacity + kBlock - 1) / kBlock), 1, geo);
+    tcp_sender_descs<<<grid, kBlock, 0, stream>>>(stride, first_slot, capacity, conn_ids, n, senders, n_conns,
+                                                  scratch.prefix, scratch.before, tick, descs);
+    return hipGetLastError();
+}
+
+// the tick's fill: launch_fill's grids, kernels' loops and store policy with `capacity` buffers and the stride as the
+// length hint (the buffer count is on the device)
+hipError_t launch_tcp_sender_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t stride, uint32_t capacity,
+                                  const cts_buf_desc* descs, const cts_tcp_sender_tick* tick, hipStream_t stream,
+                                  const LaunchGeometry& geo)
+{
+    if (capacity == 0) return hipSuccess;
+    const bool small = stride <= (uint32_t)geo.small_threshold;
+    const bool nts = geo.fill_nt == 2 ? small : geo.fill_nt != 0;
+    with_flags(
+        [&](auto NTS) {
+            if (!small) {
+                const PieceGrid pg = piece_fill_grid(capacity, stride, geo.num_cus, geo.fill_blocks_per_cu);
+                tcp_sender_fill_pieces<NTS.value><<<pg.grid, kBlock, 0, stream>>>(arena, arena_bytes, descs, tick,
+                                                                                 capacity, pg.ppb);
+            } else {
+                tcp_sender_fill_small<NTS.value><<<grid_for(capacity, kBlock / 64, geo), kBlock, 0, stream>>>(
+                    arena, arena_bytes, descs, tick, capacity);
+            }
+        },
+        nts);
     return hipGetLastError();
 }
 

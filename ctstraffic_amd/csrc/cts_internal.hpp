@@ -9,6 +9,7 @@
 #include "cts_media_stream.h"
 #include "cts_media_stream_conns.h"
 #include "cts_media_stream_servers.h"
+#include "cts_tcp_senders.h"
 
 namespace cts {
 
@@ -228,8 +229,43 @@ hipError_t launch_ms_server_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t 
                                  const cts_ms_server_tick* tick, int64_t qpc, int64_t qpf, cts_buf_desc* descs,
                                  uint32_t* lengths, hipStream_t stream, const LaunchGeometry& geo);
 
+// TCP senders on the device (cts_tcp_senders.cpp). The planning is the servers' in the same tiles; a tick's scratch
+// holds, in this order, the listed connections' exclusive prefix of wanted slots and its grand total (n + 1 words),
+// the tiles' sums, each listed connection's bytes_sent from before the tick moved its entry (n words), and a tick
+// block for the caller that passes none.
+struct TcpSenderScratch {
+    uint64_t* prefix;           // n + 1
+    uint64_t* sums;             // ms_server_tiles(n)
+    uint64_t* before;           // n
+    cts_tcp_sender_tick* tick;  // 1
+    TcpSenderScratch(void* base, uint32_t n)
+        : prefix(static_cast<uint64_t*>(base)), sums(prefix + (uint64_t)n + 1), before(sums + ms_server_tiles(n)),
+          tick(reinterpret_cast<cts_tcp_sender_tick*>(before + n))
+    {
+    }
+    static size_t bytes(uint32_t n)
+    {
+        return (size_t)((2 * (uint64_t)n + 1 + ms_server_tiles(n)) * sizeof(uint64_t) + sizeof(cts_tcp_sender_tick));
+    }
+};
+// The planning (three launches: tile sums, ms_server_scan, apply) writes scratch.prefix and scratch.before, the codes
+// (may be null), `tick` (zeroed first) and the sent block (may be null), and moves the entries of the connections that
+// take a slot. The descriptor pass reads them and tick->buffers and writes descs[0 .. tick->buffers); the fill runs
+// over those descriptors. Both grids come from `capacity`: launch_fill's rules with the stride as the length hint.
+hipError_t launch_tcp_sender_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
+                                  cts_tcp_sender_state* senders, uint32_t n_conns, uint32_t stride, uint32_t capacity,
+                                  uint32_t* codes, cts_tcp_sender_tick* tick, uint64_t* sent_counters,
+                                  const TcpSenderScratch& scratch, hipStream_t stream);
+hipError_t launch_tcp_sender_descs(uint32_t stride, uint64_t first_slot, uint32_t capacity, const uint32_t* conn_ids,
+                                   uint32_t n, const cts_tcp_sender_state* senders, uint32_t n_conns,
+                                   const TcpSenderScratch& scratch, const cts_tcp_sender_tick* tick,
+                                   cts_buf_desc* descs, hipStream_t stream, const LaunchGeometry& geo);
+hipError_t launch_tcp_sender_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t stride, uint32_t capacity,
+                                  const cts_buf_desc* descs, const cts_tcp_sender_tick* tick, hipStream_t stream,
+                                  const LaunchGeometry& geo);
+
 // The engine's device and launch geometry for the entry points that live outside cts_engine.cpp (cts_refview.cpp,
-// cts_connections.cpp, cts_media_stream_conns.cpp, cts_media_stream_servers.cpp);
+// cts_connections.cpp, cts_media_stream_conns.cpp, cts_media_stream_servers.cpp, cts_tcp_senders.cpp);
 // e != nullptr. Defined in cts_engine.cpp, where cts_engine is complete.
 const LaunchGeometry& engine_geometry(const cts_engine* e, int* device);
 

@@ -28,6 +28,9 @@ CLOSE_FIELDS = ("connections_closed", "successful", "data_errors", "not_all_data
 # the six words of a UDP block (cts_counters_udp, accumulated by the MediaStream connections' accounting pass and
 # render tick): the node-wide UdpStatusDetails (ctsConfig.h:417) plus the datagrams completed
 UDP_FIELDS = ("bits_received", "successful_frames", "dropped_frames", "duplicate_frames", "error_frames", "datagrams")
+# the six words of a sent block (cts_counters_sent, accumulated by the TCP senders' ticks): bytes_sent is the
+# TcpStatusDetails.m_bytesSent delta (ctsIOPattern.cpp:510); the last three words stay 0
+SENT_FIELDS = ("bytes_sent", "buffers_sent", "connections_finished", "reserved0", "reserved1", "reserved2")
 
 
 def dist_env():
@@ -74,8 +77,9 @@ def fold_counters(counter_block, fields=COUNTER_FIELDS):
     """Device counter block (CTS_COUNTER_SHARDS x 8 int64, cts_counters_device_bytes) -> int64[len(fields)], on the
     block's own device (no host round trip). fields=COUNTER_FIELDS_EX adds the DataError count (connections_failed,
     counted by the verifies given a conn_first_fail array); fields=REF_FIELDS folds a reference-view block and
-    fields=CLOSE_FIELDS a close block, fields=UDP_FIELDS a UDP block."""
-    assert tuple(fields) in (COUNTER_FIELDS_EX[: len(fields)], REF_FIELDS, CLOSE_FIELDS, UDP_FIELDS), fields
+    fields=CLOSE_FIELDS a close block, fields=UDP_FIELDS a UDP block, fields=SENT_FIELDS a sent block."""
+    assert tuple(fields) in (COUNTER_FIELDS_EX[: len(fields)], REF_FIELDS, CLOSE_FIELDS, UDP_FIELDS,
+                             SENT_FIELDS), fields
     return counter_block.view(-1, COUNTER_SLOTS)[:, : len(fields)].sum(0)
 
 
@@ -133,5 +137,5 @@ def gather_rank_rows(row, group=None) -> list:
     return [r.tolist() for r in rows]
 
 
-__all__ = ["dist_env", "init", "new_cpu_group", "DEFAULT_TIMEOUT_S", "REF_FIELDS", "CLOSE_FIELDS", "UDP_FIELDS", "fold_counters", "allreduce_counters", "counters_dict", "max_over_ranks",
+__all__ = ["dist_env", "init", "new_cpu_group", "DEFAULT_TIMEOUT_S", "REF_FIELDS", "CLOSE_FIELDS", "UDP_FIELDS", "SENT_FIELDS", "fold_counters", "allreduce_counters", "counters_dict", "max_over_ranks",
            "data_error_count", "gather_rank_rows"]

@@ -12,8 +12,8 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import (CtsAllreduceSetup, CtsCounters, CtsCountersClose, CtsCountersEx, CtsCountersRef, CtsCountersUdp,
-                   CtsVerifyResult, check, lib)
+from ._lib import (CtsAllreduceSetup, CtsCounters, CtsCountersClose, CtsCountersEx, CtsCountersRef, CtsCountersSent,
+                   CtsCountersUdp, CtsVerifyResult, check, lib)
 from .types import CONN_RESULT_DTYPE, CONN_STATE_DTYPE, DESC_DTYPE, RESULT_DTYPE
 
 try:
@@ -171,6 +171,23 @@ def counters_allreduce_udp(engines: Sequence["Engine"], blocks, streams=None) ->
     E, C, S, n = _multi_args(engines, blocks, streams)
     out = CtsCountersUdp()
     check("cts_counters_allreduce_udp", lib().cts_counters_allreduce_udp(E, C, S, n, ctypes.byref(out)))
+    return out.as_dict()
+
+
+def counters_read_multi_sent(engines: Sequence["Engine"], blocks, streams=None) -> dict:
+    """cts_counters_read_multi_sent: the node-wide bytes and buffers sent (the TCP senders' sent blocks), folded on
+    the host."""
+    E, C, S, n = _multi_args(engines, blocks, streams)
+    out = CtsCountersSent()
+    check("cts_counters_read_multi_sent", lib().cts_counters_read_multi_sent(E, C, S, n, ctypes.byref(out)))
+    return out.as_dict()
+
+
+def counters_allreduce_sent(engines: Sequence["Engine"], blocks, streams=None) -> dict:
+    """cts_counters_allreduce_sent: the node-wide sent counts reduced on the GPUs (the same u64 x 6 over RCCL)."""
+    E, C, S, n = _multi_args(engines, blocks, streams)
+    out = CtsCountersSent()
+    check("cts_counters_allreduce_sent", lib().cts_counters_allreduce_sent(E, C, S, n, ctypes.byref(out)))
     return out.as_dict()
 
 
@@ -429,6 +446,13 @@ class Engine:
         c = CtsCountersUdp()
         check("cts_counters_read_udp", self._L.cts_counters_read_udp(self._h, _ptr(udp_counters), ctypes.byref(c),
                                                                    _stream(stream)))
+        return c.as_dict()
+
+    def read_counters_sent(self, sent_counters, stream=None) -> dict:
+        """cts_counters_read_sent: a sent block (tcp_senders.SenderTable) folded, as cts_counters_sent."""
+        c = CtsCountersSent()
+        check("cts_counters_read_sent", self._L.cts_counters_read_sent(self._h, _ptr(sent_counters), ctypes.byref(c),
+                                                                     _stream(stream)))
         return c.as_dict()
 
     def new_results(self, n: int):

@@ -1,0 +1,118 @@
+"""TCP senders on the device-resident path (include/cts_tcp_senders.h): the entry initialiser, the tick, and a table
+that holds what a tick needs.
+
+A sender is a 32-byte entry per connection slot (types.TCP_SENDER_DTYPE); one :func:`senders_send` writes up to
+``max_buffers`` buffers of every listed connection into consecutive arena slots, with their descriptors, and the
+receive half (Engine.verify with a base_index, Engine.refview_conns, Engine.conns_close) runs over those descriptors
+unchanged. The model of a tick is workload.tcp_sender_view.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from ._lib import check, lib
+from .types import DESC_DTYPE, TCP_SENDER_DTYPE, TCP_SENDER_TICK_DTYPE
+
+
+def sender_init(transfer_bytes: int, buffer_size: int) -> np.ndarray:
+    """cts_tcp_sender_init: a fresh cts_tcp_sender_state (one TCP_SENDER_DTYPE record). Raises CtsError for a
+    transfer or a buffer size of 0."""
+    out = np.zeros(1, dtype=TCP_SENDER_DTYPE)
+    check("cts_tcp_sender_init", lib().cts_tcp_sender_init(transfer_bytes, buffer_size, out.ctypes.data))
+    return out[0]
+
+
+def senders_scratch_bytes(n: int) -> int:
+    """cts_tcp_senders_scratch_bytes: the scratch a tick over n listed connections needs."""
+    return int(lib().cts_tcp_senders_scratch_bytes(n))
+
+
+def senders_send(engine, arena, stride: int, first_slot: int, capacity: int, conn_ids, max_buffers: int, senders,
+                 n_conns: int, descs, scratch, codes=None, tick=None, sent_counters=None, stream=None, n: int = None,
+                 arena_bytes: int = None, scratch_bytes: int = None) -> None:
+    """cts_tcp_senders_send: one tick of the connections conn_ids (uint32/int32 device tensor, distinct) into slots
+    first_slot .. of arena. descs (24 bytes per slot of the capacity) is required; codes (4 bytes per id), tick (32
+    bytes) and sent_counters are device tensors or None. Raises CtsError(CTS_E_INVALID) for a refused argument."""
+    from .engine import _nbytes, _ptr, _stream
+
+    n = _nbytes(conn_ids) // 4 if n is None else n
+    check("cts_tcp_senders_send",
+          engine._L.cts_tcp_senders_send(
+              engine._h, _ptr(arena), _nbytes(arena) if arena_bytes is None else arena_bytes, stride, first_slot,
+              capacity, _ptr(conn_ids), n, max_buffers, _ptr(senders), n_conns, _ptr(descs), _ptr(codes), _ptr(tick),
+              _ptr(sent_counters), _ptr(scratch), _nbytes(scratch) if scratch_bytes is None else scratch_bytes,
+              _stream(stream)))
+
+
+class SenderTable:
+    """Many TCP senders on one device: the entry table, a tick's scratch, the arena with its descriptors, the codes,
+    the tick block and the sent block, with the tick as a method.
+
+    settings: (transfer_bytes, buffer_size) per connection slot. The arena holds arena_slots slots of stride bytes
+    (pre-filled with `fill`), a tick writes at most capacity of them from first_slot on. ``descs_of(n)`` is the
+    descriptor array of the tick's first n buffers for the receive half, with n computed from the settings: nothing is
+    read back between the send and the receive pass."""
+
+    def __init__(self, engine, settings, stride: int, capacity: int, arena_slots: int = None, device=None,
+                 fill: int = 0, max_listed: int = None):
+        import torch
+
+        self.engine = engine
+        self.device = device or "cuda:%d" % engine.device
+        self.fresh = np.zeros(len(settings), dtype=TCP_SENDER_DTYPE)
+        for c, (transfer, buffer_size) in enumerate(settings):
+            self.fresh[c] = sender_init(transfer, buffer_size)
+        self.n_conns, self.stride, self.capacity = len(settings), stride, capacity
+        self.arena_slots = capacity if arena_slots is None else arena_slots
+        words = max(1, self.n_conns) * (TCP_SENDER_DTYPE.itemsize // 8)
+        self.senders = torch.zeros(words, dtype=torch.int64, device=self.device)
+        if self.n_conns:
+            self.senders.copy_(torch.from_numpy(self.fresh.view(np.int64).copy()))
+        self.max_listed = max(1, self.n_conns if max_listed is None else max_listed)
+        self.scratch = torch.zeros((senders_scratch_bytes(self.max_listed) + 7) // 8, dtype=torch.int64,
+                                   device=self.device)
+        self.arena = torch.full((max(16, self.arena_slots * stride),), fill, dtype=torch.uint8, device=self.device)
+        self.descs = torch.zeros(max(1, capacity) * (DESC_DTYPE.itemsize // 8), dtype=torch.int64, device=self.device)
+        self.codes = torch.zeros(self.max_listed, dtype=torch.int32, device=self.device)
+        self.tick = torch.zeros(TCP_SENDER_TICK_DTYPE.itemsize // 8, dtype=torch.int64, device=self.device)
+        self.sent = engine.new_counters()
+
+    def send(self, conn_ids, max_buffers: int, first_slot: int = 0, stream=None, capacity: int = None) -> None:
+        """One tick of conn_ids (uint32/int32 device tensor, distinct, at most max_listed of them)."""
+        from .engine import _nbytes
+
+        n = _nbytes(conn_ids) // 4
+        if n > self.codes.numel():
+            raise ValueError("%d ids listed, the table's codes and scratch hold %d" % (n, self.codes.numel()))
+        capacity = self.capacity if capacity is None else capacity
+        if capacity > self.capacity:
+            raise ValueError("capacity %d, the table's descriptors hold %d" % (capacity, self.capacity))
+        senders_send(self.engine, self.arena, self.stride, first_slot, capacity, conn_ids, max_buffers, self.senders,
+                     self.n_conns, self.descs, self.scratch, codes=self.codes, tick=self.tick,
+                     sent_counters=self.sent, stream=stream)
+
+    def load(self, entries: np.ndarray) -> None:
+        """Write entries (TCP_SENDER_DTYPE[n_conns]) over the table: a transfer resumed, or a test's preset."""
+        import torch
+
+        e = np.ascontiguousarray(entries, dtype=self.fresh.dtype)
+        if len(e) != self.n_conns:
+            raise ValueError("%d entries for a table of %d" % (len(e), self.n_conns))
+        if self.n_conns:
+            self.senders.copy_(torch.from_numpy(e.view(np.int64).copy()))
+
+    def descs_of(self, n: int):
+        """The descriptors of the last tick's first n buffers (a view)."""
+        return self.descs[: n * (DESC_DTYPE.itemsize // 8)]
+
+    def read(self):
+        """(entries TCP_SENDER_DTYPE, codes uint32, tick: one TCP_SENDER_TICK_DTYPE record) copied to the host."""
+        return (self.senders.cpu().numpy().view(self.fresh.dtype)[: self.n_conns],
+                self.codes.cpu().numpy().view(np.uint32), self.tick.cpu().numpy().view(TCP_SENDER_TICK_DTYPE)[0])
+
+    def read_arena(self):
+        """(arena bytes, descriptors DESC_DTYPE[capacity]) copied to the host."""
+        return self.arena.cpu().numpy(), self.descs.cpu().numpy().view(DESC_DTYPE)[: self.capacity]
+
+    def read_sent(self, stream=None) -> dict:
+        return self.engine.read_counters_sent(self.sent, stream=stream)

@@ -157,3 +157,30 @@ MS_SERVER_TICK_DTYPE = np.dtype(
 MS_SERVER_SENT, MS_SERVER_FINISHED, MS_SERVER_ENDED, MS_SERVER_NO_ROOM, MS_SERVER_SKIPPED = 0, 1, 2, 3, 4
 MS_SERVER_MIN_DATAGRAM = 53  # CTS_MS_SERVER_MIN_DATAGRAM
 assert MS_SERVER_STATE_DTYPE.itemsize == 48 and MS_SERVER_TICK_DTYPE.itemsize == 32
+# cts_tcp_sender_state (include/cts_tcp_senders.h): one TCP sender's device entry
+TCP_SENDER_DTYPE = np.dtype(
+    [
+        ("bytes_sent", "<u8"),
+        ("transfer_bytes", "<u8"),
+        ("buffers_sent", "<u8"),
+        ("buffer_size", "<u4"),
+        ("finished", "<u4"),
+    ]
+)
+# cts_tcp_sender_tick: what one cts_tcp_senders_send did
+TCP_SENDER_TICK_DTYPE = np.dtype(
+    [
+        ("bytes", "<u8"),
+        ("buffers", "<u4"),
+        ("connections_sent", "<u4"),
+        ("connections_finished", "<u4"),
+        ("connections_no_room", "<u4"),
+        ("connections_skipped", "<u4"),
+        ("reserved", "<u4"),
+    ]
+)
+# a tick's per-connection codes
+TCP_SENDER_SENT, TCP_SENDER_FINISHED, TCP_SENDER_ENDED, TCP_SENDER_NO_ROOM, TCP_SENDER_SKIPPED = 0, 1, 2, 3, 4
+# cts_counters_sent: the six words of a sent block (the last three stay 0)
+SENT_FIELDS = ("bytes_sent", "buffers_sent", "connections_finished", "reserved0", "reserved1", "reserved2")
+assert TCP_SENDER_DTYPE.itemsize == 32 and TCP_SENDER_TICK_DTYPE.itemsize == 32

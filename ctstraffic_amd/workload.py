@@ -856,3 +856,101 @@ def media_stream_server_view(entries: np.ndarray, stride: int, ring: np.ndarray,
     """A model of the device-resident MediaStream servers over `entries` (media_stream_server_entries) and a ring of
     stride-byte slots; see MediaStreamServerView."""
     return MediaStreamServerView(entries, stride, ring, capacity)
+
+
+# ---- TCP senders on the device-resident path (include/cts_tcp_senders.h) ----------------------------------------
+TCP_SENDER_TICK_FIELDS = ("bytes", "buffers", "connections_sent", "connections_finished", "connections_no_room",
+                          "connections_skipped")
+SENT_FIELDS = ("bytes_sent", "buffers_sent", "connections_finished", "reserved0", "reserved1", "reserved2")
+
+
+def tcp_sender_entries(settings):
+    """cts_tcp_sender_init as a model, for a list of (transfer_bytes, buffer_size). Returns
+    TCP_SENDER_DTYPE[len(settings)]; raises ValueError where cts_tcp_sender_init returns CTS_E_INVALID."""
+    from .types import TCP_SENDER_DTYPE
+
+    e = np.zeros(len(settings), dtype=TCP_SENDER_DTYPE)
+    for c, (transfer, buffer_size) in enumerate(settings):
+        if transfer <= 0 or buffer_size <= 0 or transfer >= 1 << 64 or buffer_size >= 1 << 32:
+            raise ValueError("connection %d: transfer %d, buffer size %d" % (c, transfer, buffer_size))
+        e[c]["transfer_bytes"] = transfer
+        e[c]["buffer_size"] = buffer_size
+    return e
+
+
+@dataclass
+class TcpSenderTickView:
+    """What one cts_tcp_senders_send leaves behind (tcp_sender_view)."""
+    arena: np.ndarray     # the arena's bytes after the tick
+    descs: np.ndarray     # DESC_DTYPE[capacity]: [0, total) the tick's, the rest as before
+    codes: np.ndarray     # uint32 per listed id
+    tick: dict            # TCP_SENDER_TICK_FIELDS
+    counters: dict        # SENT_FIELDS: the sent block after the tick
+    entries: np.ndarray   # TCP_SENDER_DTYPE after the tick
+    prefix: np.ndarray    # uint64 per listed id: its first tick-local slot
+    taken: np.ndarray     # uint64 per listed id: the slots it took
+
+
+def tcp_sender_view(entries: np.ndarray, stride: int, arena: np.ndarray, first_slot: int, capacity: int, ids,
+                    max_buffers: int, descs: np.ndarray = None, counters: dict = None) -> TcpSenderTickView:
+    """One tick of cts_tcp_senders_send as a model, in numpy closed forms over the listed connections and over the
+    tick's buffers (the only Python loop runs over the distinct buffer lengths). arena, descs (what dev_descs held
+    before, default zeros) and counters (the sent block before, default zeros) are not modified; the results are
+    copies."""
+    from .types import TCP_SENDER_DTYPE
+
+    e = np.array(entries, dtype=TCP_SENDER_DTYPE, copy=True)
+    ids = np.array([int(x) for x in ids], dtype=np.uint64)
+    n, n_conns = len(ids), len(e)
+    table = e if n_conns else np.zeros(1, dtype=TCP_SENDER_DTYPE)
+    valid = ids < np.uint64(n_conns)
+    c = np.where(valid, ids, np.uint64(0)).astype(np.int64)
+    B = table["buffer_size"][c].astype(np.uint64)
+    sent, transfer = table["bytes_sent"][c].astype(np.uint64), table["transfer_bytes"][c].astype(np.uint64)
+    skipped = ~valid | (B == 0) | (B > np.uint64(stride))
+    ended = ~skipped & ((table["finished"][c] != 0) | (sent >= transfer))
+    running = ~skipped & ~ended
+    Bd = np.where(B == 0, np.uint64(1), B)
+    R = np.where(running, transfer - np.where(running, sent, np.uint64(0)), np.uint64(0))
+    k = R // Bd + (R % Bd != 0).astype(np.uint64)
+    w = np.where(running, np.minimum(k, np.uint64(max_buffers)), np.uint64(0))
+    p = np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(w, dtype=np.uint64)])[:n]
+    cap = np.uint64(capacity)
+    t = np.minimum(w, cap - np.minimum(p, cap))
+    moved = np.minimum(t * B, R)
+    finished = running & (t > 0) & (moved == R)
+    codes = np.zeros(n, dtype=np.uint32)
+    codes[skipped], codes[ended], codes[running & (t == 0)], codes[finished] = 4, 2, 3, 1
+    took = running & (t > 0)
+    total = int(t.sum())
+    tick = {"bytes": int(moved[took].sum()), "buffers": total, "connections_sent": int(took.sum()),
+            "connections_finished": int(finished.sum()), "connections_no_room": int((running & (t == 0)).sum()),
+            "connections_skipped": int((skipped | ended).sum())}
+    # the buffers: listed connection `owner` of tick-local slot g, its buffer j
+    owner = np.repeat(np.arange(n, dtype=np.int64), t.astype(np.int64))
+    g = np.arange(total, dtype=np.uint64)
+    j = g - p[owner]
+    start = sent[owner] + j * B[owner]
+    length = np.minimum(B[owner], transfer[owner] - start)
+    offset = start & np.uint64(PATTERN_PERIOD - 1)
+    out_descs = np.zeros(capacity, dtype=DESC_DTYPE) if descs is None else np.array(descs, dtype=DESC_DTYPE, copy=True)
+    d = out_descs[:total]
+    d["byte_offset"] = (np.uint64(first_slot) + g) * np.uint64(stride)
+    d["length"], d["expected_pattern_offset"], d["conn_index"], d["skip_head"] = length, offset, ids[owner], 0
+    out = np.array(arena, dtype=np.uint8, copy=True)
+    rows = out[: len(out) // stride * stride].reshape(-1, stride)
+    P = _pattern_prefix(PATTERN_PERIOD)
+    for L in np.unique(length):
+        L = int(L)
+        mine = np.nonzero(length == np.uint64(L))[0]
+        tiled = np.tile(P, (PATTERN_PERIOD + L - 1) // PATTERN_PERIOD + 1)[: PATTERN_PERIOD + L - 1]
+        windows = np.lib.stride_tricks.sliding_window_view(tiled, L)
+        rows[first_slot + mine, :L] = windows[offset[mine].astype(np.int64)]
+    e["bytes_sent"][c[took]] = sent[took] + moved[took]
+    e["buffers_sent"][c[took]] = e["buffers_sent"][c[took]] + t[took]
+    e["finished"][c[finished]] = 1
+    after = dict.fromkeys(SENT_FIELDS, 0) if counters is None else dict(counters)
+    after["bytes_sent"] += tick["bytes"]
+    after["buffers_sent"] += total
+    after["connections_finished"] += tick["connections_finished"]
+    return TcpSenderTickView(out, out_descs, codes, tick, after, e, p, t)
