@@ -264,6 +264,29 @@ hipError_t launch_tcp_sender_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t
                                   const cts_buf_desc* descs, const cts_tcp_sender_tick* tick, hipStream_t stream,
                                   const LaunchGeometry& geo);
 
+// The paced tick (cts_tcp_senders_send_paced; kernels in cts_tcp_paced.hip). Its scratch is the plain tick's with the
+// 48-byte tick block at the end, so a TcpSenderScratch over the same base names the same prefix, sums and before,
+// and the descriptor pass and the fill read the paced block's first 32 bytes as the plain tick they expect.
+struct TcpPacedScratch {
+    TcpSenderScratch plain;
+    cts_tcp_sender_paced_tick* tick;  // 1
+    TcpPacedScratch(void* base, uint32_t n)
+        : plain(base, n), tick(reinterpret_cast<cts_tcp_sender_paced_tick*>(plain.tick))
+    {
+    }
+    static size_t bytes(uint32_t n)
+    {
+        return TcpSenderScratch::bytes(n) - sizeof(cts_tcp_sender_tick) + sizeof(cts_tcp_sender_paced_tick);
+    }
+};
+// The paced planning (three launches: tile sums, the paced scan, apply): what launch_tcp_sender_plan writes, with the
+// wanted slots cut by the pace entries at now_ms, the pace entries moved, and the tick's 16-byte tail.
+hipError_t launch_tcp_paced_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
+                                 cts_tcp_sender_state* senders, cts_tcp_sender_pace* pace, uint32_t n_conns,
+                                 int64_t now_ms, uint32_t stride, uint32_t capacity, uint32_t* codes,
+                                 cts_tcp_sender_paced_tick* tick, uint64_t* sent_counters,
+                                 const TcpPacedScratch& scratch, hipStream_t stream);
+
 // The engine's device and launch geometry for the entry points that live outside cts_engine.cpp (cts_refview.cpp,
 // cts_connections.cpp, cts_media_stream_conns.cpp, cts_media_stream_servers.cpp, cts_tcp_senders.cpp);
 // e != nullptr. Defined in cts_engine.cpp, where cts_engine is complete.

@@ -1,5 +1,6 @@
 // cts_tcp_senders.cpp — TCP senders on the device-resident path (cts_tcp_senders.h): the host-side entry initialiser
-// (cts_tcp_sender_init), the scratch size, the tick (cts_tcp_senders_send) and the three reads of a sent block.
+// (cts_tcp_sender_init), the scratch size, the tick (cts_tcp_senders_send), the pace entry's initialiser and the paced
+// tick (cts_tcp_sender_pace_init, cts_tcp_senders_send_paced), and the three reads of a sent block.
 //
 // A translation unit of its own, like cts_media_stream_servers.cpp: nothing else in the library references these
 // entry points or their launchers. No threads, no allocation.
@@ -10,6 +11,9 @@
 
 static_assert(sizeof(cts_tcp_sender_state) == 32 && alignof(cts_tcp_sender_state) == 8, "cts_tcp_sender_state: 32 bytes");
 static_assert(sizeof(cts_tcp_sender_tick) == 32 && alignof(cts_tcp_sender_tick) == 8, "cts_tcp_sender_tick: 32 bytes");
+static_assert(sizeof(cts_tcp_sender_pace) == 64 && alignof(cts_tcp_sender_pace) == 8, "cts_tcp_sender_pace: 64 bytes");
+static_assert(sizeof(cts_tcp_sender_paced_tick) == 48 && alignof(cts_tcp_sender_paced_tick) == 8,
+              "cts_tcp_sender_paced_tick: 48 bytes");
 static_assert(sizeof(cts_counters_sent) == 6 * sizeof(uint64_t), "a sent block's six words are a counter block's");
 
 namespace {
@@ -89,6 +93,65 @@ int cts_tcp_senders_send(cts_engine* e, void* dev_arena, uint64_t arena_bytes, u
     if (rc != hipSuccess) return CTS_E_HIP;
     return hip_status(cts::launch_tcp_sender_fill(static_cast<uint8_t*>(dev_arena), arena_bytes, stride, capacity,
                                                   dev_descs, tick, s, geo));
+}
+
+int cts_tcp_sender_pace_init(uint64_t bytes_per_second, uint32_t period_ms, uint32_t burst_count,
+                             uint32_t burst_delay_ms, int64_t start_ms, cts_tcp_sender_pace* out)
+{
+    if (out == nullptr || start_ms < 0) return CTS_E_INVALID;
+    // m_quantumPeriodMs and m_bytesSendingPerQuantum as the pattern's constructor sets them (ctsIOPattern.cpp:258-262)
+    const uint32_t period = period_ms != 0u ? period_ms : 100u;
+    if (bytes_per_second > (uint64_t)INT64_MAX / period) return CTS_E_INVALID;
+    *out = cts_tcp_sender_pace{};
+    out->bytes_per_quantum = (int64_t)(bytes_per_second * period / 1000u);
+    out->quantum_start_ms = start_ms;
+    out->quantum_period_ms = period;
+    out->burst_count = burst_count;
+    out->burst_left = burst_count;
+    out->burst_delay_ms = burst_delay_ms;
+    return CTS_OK;
+}
+
+size_t cts_tcp_senders_paced_scratch_bytes(uint32_t n) { return cts::TcpPacedScratch::bytes(n); }
+
+int cts_tcp_senders_send_paced(cts_engine* e, void* dev_arena, uint64_t arena_bytes, uint32_t stride,
+                               uint64_t first_slot, uint32_t capacity, const uint32_t* dev_conn_ids, uint32_t n,
+                               uint32_t max_buffers, cts_tcp_sender_state* dev_senders, cts_tcp_sender_pace* dev_pace,
+                               uint32_t n_conns, int64_t now_ms, cts_buf_desc* dev_descs, uint32_t* dev_codes,
+                               cts_tcp_sender_paced_tick* dev_tick, void* dev_sent_counters, void* dev_scratch,
+                               size_t scratch_bytes, void* stream)
+{
+    if (e == nullptr) return CTS_E_INVALID;
+    if (n == 0) return CTS_OK;
+    if ((stride & 15u) != 0u || stride < 16u || stride > (16u << 20)) return CTS_E_INVALID;
+    if (max_buffers == 0u || now_ms < 0) return CTS_E_INVALID;
+    if (dev_arena == nullptr || misaligned(dev_arena, 16)) return CTS_E_INVALID;
+    if (first_slot > arena_bytes / stride || (uint64_t)capacity > arena_bytes / stride - first_slot)
+        return CTS_E_INVALID;
+    if (dev_conn_ids == nullptr || misaligned(dev_conn_ids, 4)) return CTS_E_INVALID;
+    if ((n_conns != 0 && dev_senders == nullptr) || misaligned(dev_senders, 8)) return CTS_E_INVALID;
+    if ((n_conns != 0 && dev_pace == nullptr) || misaligned(dev_pace, 8)) return CTS_E_INVALID;
+    if (dev_descs == nullptr || misaligned(dev_descs, 8)) return CTS_E_INVALID;
+    if (misaligned(dev_codes, 4) || misaligned(dev_tick, 8) || misaligned(dev_sent_counters, 8)) return CTS_E_INVALID;
+    if (dev_scratch == nullptr || misaligned(dev_scratch, 8) || scratch_bytes < cts::TcpPacedScratch::bytes(n))
+        return CTS_E_INVALID;
+    int device = 0;
+    const cts::LaunchGeometry& geo = cts::engine_geometry(e, &device);
+    DeviceGuard g(device);
+    if (!g.ok) return CTS_E_HIP;
+    const cts::TcpPacedScratch scratch(dev_scratch, n);
+    cts_tcp_sender_paced_tick* const tick = dev_tick != nullptr ? dev_tick : scratch.tick;
+    hipStream_t const s = static_cast<hipStream_t>(stream);
+    hipError_t rc = cts::launch_tcp_paced_plan(dev_conn_ids, n, max_buffers, dev_senders, dev_pace, n_conns, now_ms,
+                                               stride, capacity, dev_codes, tick,
+                                               static_cast<uint64_t*>(dev_sent_counters), scratch, s);
+    if (rc != hipSuccess) return CTS_E_HIP;
+    // the descriptor pass and the fill are the plain tick's: they read the block's first 32 bytes
+    rc = cts::launch_tcp_sender_descs(stride, first_slot, capacity, dev_conn_ids, n, dev_senders, n_conns,
+                                      scratch.plain, &tick->tick, dev_descs, s, geo);
+    if (rc != hipSuccess) return CTS_E_HIP;
+    return hip_status(cts::launch_tcp_sender_fill(static_cast<uint8_t*>(dev_arena), arena_bytes, stride, capacity,
+                                                  dev_descs, &tick->tick, s, geo));
 }
 
 // The reads are the *_ex reads: the same fold (and the same ncclAllReduce of count 6) over a block of the same

@@ -5,13 +5,19 @@ A sender is a 32-byte entry per connection slot (types.TCP_SENDER_DTYPE); one :f
 ``max_buffers`` buffers of every listed connection into consecutive arena slots, with their descriptors, and the
 receive half (Engine.verify with a base_index, Engine.refview_conns, Engine.conns_close) runs over those descriptors
 unchanged. The model of a tick is workload.tcp_sender_view.
+
+Send pacing (-RateLimit, -BurstCount / -BurstDelay) is a second table of 64-byte entries
+(types.TCP_SENDER_PACE_DTYPE) and :func:`senders_send_paced`, which takes the time: every listed connection sends what
+its pace entry lets out at ``now_ms``, and the 48-byte tick block ends with the time of the next deferred send.
+:class:`PacedSenderTable` holds both tables; the model is workload.tcp_paced_sender_view.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from ._lib import check, lib
-from .types import DESC_DTYPE, TCP_SENDER_DTYPE, TCP_SENDER_TICK_DTYPE
+from .types import (DESC_DTYPE, TCP_SENDER_DTYPE, TCP_SENDER_PACE_DTYPE, TCP_SENDER_PACED_TICK_DTYPE,
+                    TCP_SENDER_TICK_DTYPE)
 
 
 def sender_init(transfer_bytes: int, buffer_size: int) -> np.ndarray:
@@ -42,6 +48,39 @@ def senders_send(engine, arena, stride: int, first_slot: int, capacity: int, con
               capacity, _ptr(conn_ids), n, max_buffers, _ptr(senders), n_conns, _ptr(descs), _ptr(codes), _ptr(tick),
               _ptr(sent_counters), _ptr(scratch), _nbytes(scratch) if scratch_bytes is None else scratch_bytes,
               _stream(stream)))
+
+
+def pace_init(bytes_per_second: int = 0, period_ms: int = 0, burst_count: int = 0, burst_delay_ms: int = 0,
+              start_ms: int = 0) -> np.ndarray:
+    """cts_tcp_sender_pace_init: a fresh cts_tcp_sender_pace (one TCP_SENDER_PACE_DTYPE record) whose first quantum
+    starts at start_ms. Raises CtsError for a negative start_ms or a rate x period beyond an int64."""
+    out = np.zeros(1, dtype=TCP_SENDER_PACE_DTYPE)
+    check("cts_tcp_sender_pace_init",
+          lib().cts_tcp_sender_pace_init(bytes_per_second, period_ms, burst_count, burst_delay_ms, start_ms,
+                                         out.ctypes.data))
+    return out[0]
+
+
+def senders_paced_scratch_bytes(n: int) -> int:
+    """cts_tcp_senders_paced_scratch_bytes: the scratch a paced tick over n listed connections needs."""
+    return int(lib().cts_tcp_senders_paced_scratch_bytes(n))
+
+
+def senders_send_paced(engine, arena, stride: int, first_slot: int, capacity: int, conn_ids, max_buffers: int,
+                       senders, pace, n_conns: int, now_ms: int, descs, scratch, codes=None, tick=None,
+                       sent_counters=None, stream=None, n: int = None, arena_bytes: int = None,
+                       scratch_bytes: int = None) -> None:
+    """cts_tcp_senders_send_paced: :func:`senders_send` at the time now_ms over the pace table `pace` (64 bytes per
+    connection slot); tick is 48 bytes or None. Raises CtsError(CTS_E_INVALID) for a refused argument."""
+    from .engine import _nbytes, _ptr, _stream
+
+    n = _nbytes(conn_ids) // 4 if n is None else n
+    check("cts_tcp_senders_send_paced",
+          engine._L.cts_tcp_senders_send_paced(
+              engine._h, _ptr(arena), _nbytes(arena) if arena_bytes is None else arena_bytes, stride, first_slot,
+              capacity, _ptr(conn_ids), n, max_buffers, _ptr(senders), _ptr(pace), n_conns, now_ms, _ptr(descs),
+              _ptr(codes), _ptr(tick), _ptr(sent_counters), _ptr(scratch),
+              _nbytes(scratch) if scratch_bytes is None else scratch_bytes, _stream(stream)))
 
 
 class SenderTable:
@@ -116,3 +155,63 @@ class SenderTable:
 
     def read_sent(self, stream=None) -> dict:
         return self.engine.read_counters_sent(self.sent, stream=stream)
+
+
+class PacedSenderTable(SenderTable):
+    """A SenderTable with a pace entry per connection slot and the paced tick.
+
+    settings: (transfer_bytes, buffer_size) per connection slot; pace_settings: per slot a dict of
+    :func:`pace_init`'s keywords (bytes_per_second, period_ms, burst_count, burst_delay_ms; {} = unpaced). Every
+    first quantum starts at start_ms. ``send(conn_ids, max_buffers, now_ms)`` is one paced tick; the plain tick
+    stays available as ``SenderTable.send(table, ...)`` over the same entries."""
+
+    def __init__(self, engine, settings, pace_settings, stride: int, capacity: int, start_ms: int = 0, **kw):
+        import torch
+
+        super().__init__(engine, settings, stride, capacity, **kw)
+        if len(pace_settings) != self.n_conns:
+            raise ValueError("%d pace settings for a table of %d" % (len(pace_settings), self.n_conns))
+        self.fresh_pace = np.zeros(self.n_conns, dtype=TCP_SENDER_PACE_DTYPE)
+        for c, s in enumerate(pace_settings):
+            self.fresh_pace[c] = pace_init(start_ms=start_ms, **s)
+        words = max(1, self.n_conns) * (TCP_SENDER_PACE_DTYPE.itemsize // 8)
+        self.pace = torch.zeros(words, dtype=torch.int64, device=self.device)
+        self.load_pace(self.fresh_pace)
+        self.scratch = torch.zeros((senders_paced_scratch_bytes(self.max_listed) + 7) // 8, dtype=torch.int64,
+                                   device=self.device)
+        self.tick = torch.zeros(TCP_SENDER_PACED_TICK_DTYPE.itemsize // 8, dtype=torch.int64, device=self.device)
+
+    def send(self, conn_ids, max_buffers: int, now_ms: int, first_slot: int = 0, stream=None,
+             capacity: int = None) -> None:
+        """One paced tick of conn_ids (uint32/int32 device tensor, distinct, at most max_listed of them) at now_ms."""
+        from .engine import _nbytes
+
+        n = _nbytes(conn_ids) // 4
+        if n > self.codes.numel():
+            raise ValueError("%d ids listed, the table's codes and scratch hold %d" % (n, self.codes.numel()))
+        capacity = self.capacity if capacity is None else capacity
+        if capacity > self.capacity:
+            raise ValueError("capacity %d, the table's descriptors hold %d" % (capacity, self.capacity))
+        senders_send_paced(self.engine, self.arena, self.stride, first_slot, capacity, conn_ids, max_buffers,
+                           self.senders, self.pace, self.n_conns, now_ms, self.descs, self.scratch, codes=self.codes,
+                           tick=self.tick, sent_counters=self.sent, stream=stream)
+
+    def load_pace(self, pace: np.ndarray) -> None:
+        """Write pace (TCP_SENDER_PACE_DTYPE[n_conns]) over the pace table."""
+        import torch
+
+        q = np.ascontiguousarray(pace, dtype=TCP_SENDER_PACE_DTYPE)
+        if len(q) != self.n_conns:
+            raise ValueError("%d pace entries for a table of %d" % (len(q), self.n_conns))
+        if self.n_conns:
+            self.pace.copy_(torch.from_numpy(q.view(np.int64).copy()))
+
+    def read(self):
+        """(entries, codes uint32, tick: one TCP_SENDER_PACED_TICK_DTYPE record) copied to the host."""
+        return (self.senders.cpu().numpy().view(self.fresh.dtype)[: self.n_conns],
+                self.codes.cpu().numpy().view(np.uint32),
+                self.tick.cpu().numpy().view(TCP_SENDER_PACED_TICK_DTYPE)[0])
+
+    def read_pace(self) -> np.ndarray:
+        """The pace table (TCP_SENDER_PACE_DTYPE[n_conns]) copied to the host."""
+        return self.pace.cpu().numpy().view(TCP_SENDER_PACE_DTYPE)[: self.n_conns]

@@ -184,3 +184,26 @@ TCP_SENDER_SENT, TCP_SENDER_FINISHED, TCP_SENDER_ENDED, TCP_SENDER_NO_ROOM, TCP_
 # cts_counters_sent: the six words of a sent block (the last three stay 0)
 SENT_FIELDS = ("bytes_sent", "buffers_sent", "connections_finished", "reserved0", "reserved1", "reserved2")
 assert TCP_SENDER_DTYPE.itemsize == 32 and TCP_SENDER_TICK_DTYPE.itemsize == 32
+# cts_tcp_sender_pace: one TCP sender's pacing state (a table parallel to the entries)
+TCP_SENDER_PACE_DTYPE = np.dtype(
+    [
+        ("bytes_per_quantum", "<i8"),
+        ("bytes_this_quantum", "<i8"),
+        ("quantum_start_ms", "<i8"),
+        ("due_ms", "<i8"),
+        ("quantum_period_ms", "<u4"),
+        ("burst_count", "<u4"),
+        ("burst_left", "<u4"),
+        ("burst_delay_ms", "<u4"),
+        ("pending", "<u4"),
+        ("reserved", "<u4", (3,)),
+    ]
+)
+# cts_tcp_sender_paced_tick: what one cts_tcp_senders_send_paced did; its first 32 bytes are a cts_tcp_sender_tick
+TCP_SENDER_PACED_TICK_DTYPE = np.dtype(
+    TCP_SENDER_TICK_DTYPE.descr + [("next_due_ms", "<i8"), ("connections_waiting", "<u4"),
+                                   ("connections_pending", "<u4")]
+)
+TCP_SENDER_WAITING = 5
+TCP_SENDER_NO_DUE = (1 << 63) - 1  # next_due_ms when nothing is pending
+assert TCP_SENDER_PACE_DTYPE.itemsize == 64 and TCP_SENDER_PACED_TICK_DTYPE.itemsize == 48

@@ -897,6 +897,12 @@ def tcp_sender_view(entries: np.ndarray, stride: int, arena: np.ndarray, first_s
     tick's buffers (the only Python loop runs over the distinct buffer lengths). arena, descs (what dev_descs held
     before, default zeros) and counters (the sent block before, default zeros) are not modified; the results are
     copies."""
+    return _tcp_sender_tick(entries, stride, arena, first_slot, capacity, ids, max_buffers, descs, counters, None)
+
+
+def _tcp_sender_tick(entries, stride, arena, first_slot, capacity, ids, max_buffers, descs, counters, cut):
+    """tcp_sender_view's tick. cut (None for the plain tick): cut(i, c, limit, R, B) -> the slots that listed
+    connection i (slot c, running, wanting `limit`) wants after pacing; a running connection cut to 0 gets code 5."""
     from .types import TCP_SENDER_DTYPE
 
     e = np.array(entries, dtype=TCP_SENDER_DTYPE, copy=True)
@@ -914,6 +920,11 @@ def tcp_sender_view(entries: np.ndarray, stride: int, arena: np.ndarray, first_s
     R = np.where(running, transfer - np.where(running, sent, np.uint64(0)), np.uint64(0))
     k = R // Bd + (R % Bd != 0).astype(np.uint64)
     w = np.where(running, np.minimum(k, np.uint64(max_buffers)), np.uint64(0))
+    waiting = np.zeros(n, dtype=bool)
+    if cut is not None:
+        for i in np.nonzero(running)[0]:
+            w[i] = cut(int(i), int(c[i]), int(w[i]), int(R[i]), int(B[i]))
+        waiting = running & (w == 0)
     p = np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(w, dtype=np.uint64)])[:n]
     cap = np.uint64(capacity)
     t = np.minimum(w, cap - np.minimum(p, cap))
@@ -921,10 +932,11 @@ def tcp_sender_view(entries: np.ndarray, stride: int, arena: np.ndarray, first_s
     finished = running & (t > 0) & (moved == R)
     codes = np.zeros(n, dtype=np.uint32)
     codes[skipped], codes[ended], codes[running & (t == 0)], codes[finished] = 4, 2, 3, 1
+    codes[waiting] = 5
     took = running & (t > 0)
     total = int(t.sum())
     tick = {"bytes": int(moved[took].sum()), "buffers": total, "connections_sent": int(took.sum()),
-            "connections_finished": int(finished.sum()), "connections_no_room": int((running & (t == 0)).sum()),
+            "connections_finished": int(finished.sum()), "connections_no_room": int((running & (t == 0) & ~waiting).sum()),
             "connections_skipped": int((skipped | ended).sum())}
     # the buffers: listed connection `owner` of tick-local slot g, its buffer j
     owner = np.repeat(np.arange(n, dtype=np.int64), t.astype(np.int64))
@@ -954,3 +966,138 @@ def tcp_sender_view(entries: np.ndarray, stride: int, arena: np.ndarray, first_s
     after["buffers_sent"] += total
     after["connections_finished"] += tick["connections_finished"]
     return TcpSenderTickView(out, out_descs, codes, tick, after, e, p, t)
+
+
+# ---- send pacing on the device-resident path (cts_tcp_senders_send_paced) -----------------------------------------
+TCP_SENDER_PACED_TAIL_FIELDS = ("next_due_ms", "connections_waiting", "connections_pending")
+TCP_SENDER_NO_DUE = (1 << 63) - 1
+
+
+def tcp_sender_pace_entries(settings, start_ms: int = 0):
+    """cts_tcp_sender_pace_init as a model, for a list of dicts with the keys bytes_per_second, period_ms,
+    burst_count, burst_delay_ms (each optional, default 0; {} = unpaced). Returns
+    TCP_SENDER_PACE_DTYPE[len(settings)]; raises ValueError where cts_tcp_sender_pace_init returns CTS_E_INVALID."""
+    from .types import TCP_SENDER_PACE_DTYPE
+
+    q = np.zeros(len(settings), dtype=TCP_SENDER_PACE_DTYPE)
+    for c, s in enumerate(settings):
+        unknown = set(s) - {"bytes_per_second", "period_ms", "burst_count", "burst_delay_ms"}
+        if unknown:
+            raise ValueError("connection %d: unknown pace settings %s" % (c, sorted(unknown)))
+        bps, period = s.get("bytes_per_second", 0), s.get("period_ms", 0) or 100
+        if start_ms < 0 or start_ms >= 1 << 63 or bps < 0 or bps * period >= 1 << 63:
+            raise ValueError("connection %d: rate %d, period %d, start %d" % (c, bps, period, start_ms))
+        q[c]["bytes_per_quantum"] = bps * period // 1000
+        q[c]["quantum_start_ms"] = start_ms
+        q[c]["quantum_period_ms"] = period
+        q[c]["burst_count"] = q[c]["burst_left"] = s.get("burst_count", 0)
+        q[c]["burst_delay_ms"] = s.get("burst_delay_ms", 0)
+    return q
+
+
+def _pace_step(q: dict, now: int, size: int) -> int:
+    """CreateNewTask's send branch (ctsIOPattern.cpp:593-674) over a pace entry held as a dict of Python ints: the
+    task's time offset."""
+    off = 0
+    per, period = q["bytes_per_quantum"], q["quantum_period_ms"]
+    if per > 0:
+        if q["bytes_this_quantum"] < per:
+            q["bytes_this_quantum"] += size
+            if now > q["quantum_start_ms"] + period:
+                skipped = (now - q["quantum_start_ms"]) // period
+                q["quantum_start_ms"] += skipped * period
+                adjust = per * skipped
+                q["bytes_this_quantum"] = 0 if adjust > q["bytes_this_quantum"] else q["bytes_this_quantum"] - adjust
+        else:
+            ahead = q["bytes_this_quantum"] // per
+            skip = (ahead - 1) * period
+            q["bytes_this_quantum"] += size - per * ahead
+            if now < q["quantum_start_ms"] + period:
+                off = q["quantum_start_ms"] + period - now
+            off += skip
+            q["quantum_start_ms"] += skip + period
+    elif q["burst_count"]:
+        if q["burst_left"] == 0:
+            q["burst_left"] = q["burst_count"]
+        q["burst_left"] -= 1
+        if q["burst_left"] == 0:
+            off = q["burst_delay_ms"]
+    return off
+
+
+def _pace_run(q: dict, now: int, cap: int, R: int, B: int) -> int:
+    """run(cap) of include/cts_tcp_senders.h over q (moved in place): the sends that go out at `now`."""
+    count = 0
+    while count < cap and R - count * B > 0:
+        if q["pending"]:
+            if now < q["due_ms"]:
+                break
+            q["pending"] = 0
+        else:
+            off = _pace_step(q, now, min(B, R - count * B))
+            if off > 0:
+                q["pending"], q["due_ms"] = 1, now + off
+                break
+        count += 1
+    return count
+
+
+_PACE_SCALARS = ("bytes_per_quantum", "bytes_this_quantum", "quantum_start_ms", "due_ms", "quantum_period_ms",
+                 "burst_count", "burst_left", "burst_delay_ms", "pending")
+
+
+@dataclass
+class TcpPacedSenderTickView(TcpSenderTickView):
+    """What one cts_tcp_senders_send_paced leaves behind (tcp_paced_sender_view): a TcpSenderTickView (codes with 5 =
+    waiting), and"""
+    pace: np.ndarray = None     # TCP_SENDER_PACE_DTYPE after the tick
+    waiting: np.ndarray = None  # the listed positions with code 5
+    tail: dict = None           # TCP_SENDER_PACED_TAIL_FIELDS
+    wanted: np.ndarray = None   # uint64 per listed id: w, the slots pacing lets it want
+
+
+def tcp_paced_sender_view(entries: np.ndarray, pace: np.ndarray, now_ms: int, stride: int, arena: np.ndarray,
+                          first_slot: int, capacity: int, ids, max_buffers: int, descs: np.ndarray = None,
+                          counters: dict = None) -> TcpPacedSenderTickView:
+    """One tick of cts_tcp_senders_send_paced as a model: tcp_sender_view with every running listed connection's
+    wanted slots cut by run(limit) over its pace entry (a plain Python loop per connection), the pace entries moved
+    as the header states (run(limit), or run(t) for the one connection the capacity cuts; untouched with code 3),
+    and the tick's tail. Nothing passed in is modified."""
+    from .types import TCP_SENDER_PACE_DTYPE
+
+    q_out = np.array(pace, dtype=TCP_SENDER_PACE_DTYPE, copy=True)
+    if len(q_out) != len(entries):
+        raise ValueError("%d pace entries beside %d sender entries" % (len(q_out), len(entries)))
+    moved, asked = {}, {}
+
+    def stored(c):
+        return {f: int(q_out[c][f]) for f in _PACE_SCALARS}
+
+    def cut(i, c, limit, R, B):
+        q = stored(c)
+        w = _pace_run(q, now_ms, limit, R, B)
+        moved[i], asked[i] = q, (c, R, B, w)
+        return w
+
+    v = _tcp_sender_tick(entries, stride, arena, first_slot, capacity, ids, max_buffers, descs, counters, cut)
+    wanted = np.zeros(len(v.codes), dtype=np.uint64)
+    due = []
+    for i, (c, R, B, w) in asked.items():  # q_out[c] is still the entry from before the tick: the ids are distinct
+        t, code = int(v.taken[i]), int(v.codes[i])
+        wanted[i] = w
+        if code == 3:       # no room: the stored entry stays
+            q = stored(c)
+        elif 0 < t < w:     # cut by the capacity: t steps, and no task beyond the t-th
+            q = stored(c)
+            if _pace_run(q, now_ms, t, R, B) != t:
+                raise AssertionError("run(t) stopped before t")
+        else:               # code 5 (w == 0), or everything it wanted
+            q = moved[i]
+        for f in ("bytes_this_quantum", "quantum_start_ms", "due_ms", "burst_left", "pending"):
+            q_out[c][f] = q[f]
+        if q["pending"]:
+            due.append(q["due_ms"])
+    tail = {"next_due_ms": min(due) if due else TCP_SENDER_NO_DUE, "connections_waiting": int((v.codes == 5).sum()),
+            "connections_pending": len(due)}
+    return TcpPacedSenderTickView(v.arena, v.descs, v.codes, v.tick, v.counters, v.entries, v.prefix, v.taken,
+                                  q_out, np.nonzero(v.codes == 5)[0], tail, wanted)

@@ -22,8 +22,17 @@
  * advances it by the tick's total gives every connection increasing stream ordinals in stream order, which is what
  * the first-failure slots need.
  *
+ * Send pacing (-RateLimit with its TcpBytesPerSecondPeriod quanta, -BurstCount / -BurstDelay) runs in the tick too:
+ *
+ *   per tick   cts_tcp_senders_send_paced(..., dev_pace, now_ms, ...)  -> the same, but every listed connection sends
+ *                                                              what CreateNewTask's send branch
+ *                                                              (ctsIOPattern.cpp:593-674) lets it send at now_ms, from
+ *                                                              a 64-byte pace entry per connection; the tick block
+ *                                                              ends with the time of the next deferred send
+ *
+ * so a rate-limited run lists every connection in every tick and its one host timer sleeps until next_due_ms.
+ *
  * Out of scope:
- *   - send pacing (-RateLimit, BurstCount / BurstDelay): a tick is the caller's timer
  *   - -Buffer:[lo,hi] random buffer sizes: an entry has one buffer_size
  *   - a ring that wraps: a tick writes the slots first_slot .. first_slot + total of one flat arena
  *   - handing the slots to sockets
@@ -126,6 +135,87 @@ int cts_tcp_senders_send(cts_engine* engine, void* dev_arena, uint64_t arena_byt
                          uint32_t max_buffers, cts_tcp_sender_state* dev_senders, uint32_t n_conns,
                          cts_buf_desc* dev_descs, uint32_t* dev_codes, cts_tcp_sender_tick* dev_tick,
                          void* dev_sent_counters, void* dev_scratch, size_t scratch_bytes, void* stream);
+
+/* ---- send pacing ---------------------------------------------------------------------------------------------------
+ * One per connection slot, device memory, 8-byte aligned, 64 bytes: a table parallel to dev_senders. Filled by
+ * cts_tcp_sender_pace_init on the host and copied to the device by the caller; afterwards only the paced tick writes
+ * it. The members are CreateNewTask's pacing state (ctsIOPattern.h:204-205, 273-275) plus the one send that a task
+ * with a time offset leaves waiting. */
+typedef struct cts_tcp_sender_pace {
+    int64_t bytes_per_quantum;  /* m_bytesSendingPerQuantum = bytes_per_second x period_ms / 1000; 0 = no rate limit */
+    int64_t bytes_this_quantum; /* m_bytesSendingThisQuantum */
+    int64_t quantum_start_ms;   /* m_quantumStartTimeMs */
+    int64_t due_ms;             /* when the pending send may go out; meaningful only while pending != 0 */
+    uint32_t quantum_period_ms; /* TcpBytesPerSecondPeriod */
+    uint32_t burst_count;       /* -BurstCount, the setting; 0 = none */
+    uint32_t burst_left;        /* m_burstCount */
+    uint32_t burst_delay_ms;    /* -BurstDelay */
+    uint32_t pending;           /* 1: a task has been created whose send waits for due_ms */
+    uint32_t reserved[3];       /* 0 */
+} cts_tcp_sender_pace;          /* 64 bytes */
+
+/* A fresh pace entry whose first quantum starts at start_ms. period_ms == 0 means 100. A rate whose bytes per quantum
+ * come to 0 leaves the burst settings in charge; otherwise a rate limit takes precedence over them
+ * (ctsIOPattern.cpp:593, 657). CTS_E_INVALID for a null out, a negative start_ms, or bytes_per_second x period_ms that
+ * does not fit an int64. Host only. */
+int cts_tcp_sender_pace_init(uint64_t bytes_per_second, uint32_t period_ms, uint32_t burst_count,
+                             uint32_t burst_delay_ms, int64_t start_ms, cts_tcp_sender_pace* out);
+
+#define CTS_TCP_SENDER_WAITING 5u /* running, but pacing lets no send out at now_ms: nothing sent */
+
+/* What one paced tick did. 48 bytes, 8-byte aligned. Its first 32 bytes are the plain tick's block. */
+typedef struct cts_tcp_sender_paced_tick {
+    cts_tcp_sender_tick tick;
+    int64_t next_due_ms;          /* the smallest due_ms of the listed running connections (codes 0, 1, 3 and 5) that
+                                     the tick leaves with pending != 0; INT64_MAX when there is none: the one number a
+                                     host timer needs */
+    uint32_t connections_waiting; /* code 5 */
+    uint32_t connections_pending; /* the listed running connections left with pending != 0, those that sent included */
+} cts_tcp_sender_paced_tick;
+
+/* Bytes of dev_scratch a paced tick over n listed connections needs (the plain tick's, with the larger tick block). */
+size_t cts_tcp_senders_paced_scratch_bytes(uint32_t n);
+
+/* One paced tick at the time now_ms: cts_tcp_senders_send, with every listed running connection's wanted slots cut to
+ * what its pace entry Q = dev_pace[c] lets out. Let step(now, size) be CreateNewTask's send branch
+ * (ctsIOPattern.cpp:593-674) over Q: it moves the quantum or the burst count and returns the task's time offset. With
+ * limit = min(max_buffers, ceil(R / B)):
+ *
+ *   run(cap):  count = 0
+ *     while count < cap:
+ *         if Q.pending:  if now_ms < Q.due_ms: break;  Q.pending = 0            the waiting send goes out first
+ *         else:          off = step(now_ms, min(B, R - count B))
+ *                        if off > 0: Q.pending = 1; Q.due_ms = now_ms + off; break   task created, send deferred
+ *         count += 1
+ *     return count
+ *
+ * This models a caller that stops asking a connection for tasks once one has come back with a time offset, until that
+ * send has gone out: the reference's scheduler would go on and queue further timers, which needs a timer per task.
+ *
+ * The connection wants w = run(limit) slots; p and t are the plain tick's (t = min(w, capacity - min(p, capacity))):
+ *   w == 0                       nothing sent (code 5), E untouched, Q as run(limit) leaves it (a first step may
+ *                                have created the pending task)
+ *   w > 0, t == 0                nothing sent (code 3), E and Q untouched
+ *   0 < t < w                    t buffers sent, Q as run(t) leaves it (no task beyond the t-th is created)
+ *   t == w                       w buffers sent, Q as run(limit) leaves it
+ * Codes 0-4, the buffers' bytes, the descriptors, E's update, the sent block and the no-gap rule are the plain tick's;
+ * tick.buffers = min(capacity, sum of w). Connections with codes 2 and 4 have neither entry read past what decides
+ * the code, and do not count for next_due_ms or connections_pending. A table whose pace entries all have
+ * bytes_per_quantum == 0, burst_count == 0 and pending == 0 gives, byte for byte and field for field, what
+ * cts_tcp_senders_send gives.
+ *
+ * Arguments: cts_tcp_senders_send's, and dev_pace non-null when n_conns != 0 and 8-byte aligned, n_conns entries;
+ * now_ms >= 0; dev_tick (may be NULL) a cts_tcp_sender_paced_tick; scratch_bytes >=
+ * cts_tcp_senders_paced_scratch_bytes(n). The caller's duties: now_ms does not decrease from tick to tick of a table
+ * and stays below 2^62, and bytes_per_quantum x the quanta a tick skips fits an int64; a pace entry comes from
+ * cts_tcp_sender_pace_init. Outside them the values of the pace entries, the wanted counts and the tick's tail are
+ * unspecified, but no write leaves the entries, the capacity's slots or the output arrays. */
+int cts_tcp_senders_send_paced(cts_engine* engine, void* dev_arena, uint64_t arena_bytes, uint32_t stride,
+                               uint64_t first_slot, uint32_t capacity, const uint32_t* dev_conn_ids, uint32_t n,
+                               uint32_t max_buffers, cts_tcp_sender_state* dev_senders, cts_tcp_sender_pace* dev_pace,
+                               uint32_t n_conns, int64_t now_ms, cts_buf_desc* dev_descs, uint32_t* dev_codes,
+                               cts_tcp_sender_paced_tick* dev_tick, void* dev_sent_counters, void* dev_scratch,
+                               size_t scratch_bytes, void* stream);
 
 /* The three counter reads over sent blocks: the same fold, and for the all-reduce the same ncclAllReduce of count 6,
  * with the six words named as cts_counters_sent. */
