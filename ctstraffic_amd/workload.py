@@ -1027,6 +1027,8 @@ def _pace_step(q: dict, now: int, size: int) -> int:
 
 def _pace_run(q: dict, now: int, cap: int, R: int, B: int) -> int:
     """run(cap) of include/cts_tcp_senders.h over q (moved in place): the sends that go out at `now`."""
+    if q["bytes_per_quantum"] == 0 and q["burst_count"] == 0 and not q["pending"]:
+        return min(cap, -(-R // B))  # unpaced: no step moves the entry or defers a send (a cap of 2^31 is no loop)
     count = 0
     while count < cap and R - count * B > 0:
         if q["pending"]:
