@@ -6,7 +6,7 @@
 #                      (tools/libcts_bench_multi.so, tools/pattern_cpu_probe)
 #   make probes     -> the measurement probes of tools/ (ceilings, timelines, ablations; built before an A/B call)
 #   make asm        -> ctstraffic_amd/build/<unit>-gfx950.s for every kernel unit: cts_verify, cts_media_stream_recv,
-#                      cts_fill, cts_tcp_paced, cts_accounting (disassembly for inspection; tools/kernel_text.py lists and compares
+#                      cts_fill, cts_tick_plan, cts_accounting (disassembly for inspection; tools/kernel_text.py lists and compares
 #                      the kernels in them)
 HIPCC     ?= /opt/rocm/bin/hipcc
 ARCH      ?= gfx950

@@ -1,5 +1,5 @@
 // cts_device_util.hpp — the few device-side definitions that every kernel unit (cts_verify.hip,
-// cts_media_stream_recv.hip, cts_fill.hip, cts_tcp_paced.hip, cts_accounting.hip) needs: the block size, the empty-slot value, the descriptor check, a batch's source and the wave sums.
+// cts_media_stream_recv.hip, cts_fill.hip, cts_tick_plan.hip, cts_accounting.hip) needs: the block size, the empty-slot value, the descriptor check, a batch's source and the wave sums.
 #pragma once
 
 #include <hip/hip_runtime.h>

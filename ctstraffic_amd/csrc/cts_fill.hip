@@ -1,13 +1,12 @@
-// cts_fill.hip — the sender side for gfx950: the write-bound twins of the verify kernels, and the MediaStream servers'
-// tick.
+// cts_fill.hip — the sender side for gfx950: the write-bound twins of the verify kernels.
 //   fill_kernel / fill_pieces_kernel / fill_span_kernel   the pattern into buffers (cts_fill) and one long span
 //   fill_batched_kernel / media_stream_fill_ring_kernel   whole MediaStream datagrams: descriptors, or a ring
-//   ms_server_sums / _scan / _apply, ms_server_fill   the MediaStream servers' tick: slots planned by a prefix sum over
-//                                     the listed connections, then the ring fill with media_stream_fill_ring_kernel's
+//   ms_server_fill                    the MediaStream servers' tick: the ring fill with media_stream_fill_ring_kernel's
 //                                     store loop (cts_ring_store_loop.hpp) and no per-datagram metadata
-//   tcp_sender_sums / _apply / _descs, tcp_sender_fill_pieces / _small   the TCP senders' tick: the same planning, a
-//                                     descriptor per written slot, then fill_pieces_kernel's or fill_kernel's loop
-//                                     (cts_fill_pieces_loop.hpp, cts_fill_team_loop.hpp) over a count read on the device
+//   tcp_sender_descs, tcp_sender_fill_pieces / _small   the TCP senders' tick: a descriptor per written slot, then
+//                                     fill_pieces_kernel's or fill_kernel's loop (cts_fill_pieces_loop.hpp,
+//                                     cts_fill_team_loop.hpp) over a count read on the device
+// The slots of both ticks are planned in cts_tick_plan.hip, which writes no pattern byte.
 // The expected chunk is regenerated in registers as in the verify (cts_chunks.hpp); the verify kernels are in
 // cts_verify.hip, the MediaStream receive in cts_media_stream_recv.hip. The alternatives that lost are in DESIGN.md §10.
 #include <hip/hip_runtime.h>
@@ -395,175 +394,9 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // ---------------------------------------------------------------------------------------------
-// MediaStream servers on the device (cts_media_stream_servers_send): one tick of the listed connections' frame sends
-// with no per-datagram metadata from the host. Listed connection i wants k_i = datagrams_per_frame ring slots (0 when
-// it sends nothing whatever the room); p_i, the exclusive prefix of the wants in listed order, is its first slot, and
-// it sends when p_i + k_i <= capacity. p is monotonic, so the connections that send are a prefix of those that want
-// and the tick's datagrams are the slots [0, total) with no gap. Three plain launches plan the tick, in tiles of
-// kMsServerTile listed connections (no workgroup ever waits for another):
-//   ms_server_sums    each tile's sum of wants                              -> sums[tile]
-//   ms_server_scan    one workgroup: exclusive scan of the tile sums in place, prefix[n] = the grand total, tick = 0
-//   ms_server_apply   p_i = sums[tile] + the tile's own scan -> prefix[i]; the code, the entry's update, the tick and
-//                     the UDP block of every connection that fits
-// and ms_server_fill writes the ring from prefix[] and the entries.
-// Scratch (MsServerScratch, cts_internal.hpp): u64 prefix[n + 1], u64 sums[tiles], a tick.
-
-// The slots listed connection c wants, and its code when it sends nothing whatever the room.
-__device__ __forceinline__ uint32_t ms_server_want(const cts_ms_server_state* __restrict__ servers, uint32_t c,
-                                                   uint32_t n_conns, uint32_t stride, uint32_t& code)
-{
-    code = CTS_MS_SERVER_SKIPPED;
-    if (c >= n_conns) return 0u;
-    if (servers[c].finished != 0u) {
-        code = CTS_MS_SERVER_ENDED;
-        return 0u;
-    }
-    if (servers[c].datagram_max_size > stride) return 0u;
-    code = CTS_MS_SERVER_SENT;
-    return servers[c].datagrams_per_frame;
-}
-
-// Exclusive scan of v over the workgroup's kBlock threads (wave scans, then the waves' sums through wsum); total = the
-// workgroup's sum. Ends with a barrier: wsum is free again.
-__device__ __forceinline__ uint64_t tile_scan_exclusive(uint64_t v, uint64_t* wsum, uint64_t& total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t inc = v;
-#pragma unroll
-    for (uint32_t off = 1; off < 64u; off <<= 1) {
-        const uint64_t u = (uint64_t)__shfl_up((unsigned long long)inc, off, 64);
-        if (lane >= off) inc += u;
-    }
-    if (lane == 63u) wsum[wave] = inc;
-    __syncthreads();
-    uint64_t base = 0;
-    total = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < (uint32_t)kBlock / 64u; ++w) {
-        if (w < wave) base += wsum[w];
-        total += wsum[w];
-    }
-    __syncthreads();
-    return base + inc - v;
-}
-
-static_assert(kMsServerTile == (uint32_t)kBlock, "one listed connection per thread of a tile");
-
-__global__ void __launch_bounds__(kBlock)
-    ms_server_sums(const uint32_t* __restrict__ ids, uint32_t n, const cts_ms_server_state* __restrict__ servers,
-                   uint32_t n_conns, uint32_t stride, uint64_t* __restrict__ sums)
-{
-    __shared__ uint64_t wsum[kBlock / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * kMsServerTile + threadIdx.x;
-    uint32_t code;
-    const uint64_t want = i < n ? ms_server_want(servers, ids[i], n_conns, stride, code) : 0u;
-    const uint64_t s = wave_sum64(want);
-    if ((threadIdx.x & 63u) == 0u) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-        uint64_t t = 0;
-#pragma unroll
-        for (int w = 0; w < kBlock / 64; ++w) t += wsum[w];
-        sums[blockIdx.x] = t;
-    }
-}
-
-// One workgroup. tick is 8 dwords (cts_ms_server_tick).
-__global__ void __launch_bounds__(kBlock)
-    ms_server_scan(uint64_t* __restrict__ sums, uint64_t tiles, uint64_t* __restrict__ prefix_total,
-                   uint32_t* __restrict__ tick)
-{
-    __shared__ uint64_t wsum[kBlock / 64];
-    uint64_t carry = 0;
-    for (uint64_t base = 0; base < tiles; base += kBlock) {
-        const uint64_t t = base + threadIdx.x;
-        const uint64_t v = t < tiles ? sums[t] : 0u;
-        uint64_t total;
-        const uint64_t ex = tile_scan_exclusive(v, wsum, total);
-        if (t < tiles) sums[t] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0u) *prefix_total = carry;
-    if (threadIdx.x < sizeof(cts_ms_server_tick) / 4u) tick[threadIdx.x] = 0u;
-}
-
-__global__ void __launch_bounds__(kBlock)
-    ms_server_apply(const uint32_t* __restrict__ ids, uint32_t n, cts_ms_server_state* __restrict__ servers,
-                    uint32_t n_conns, uint32_t stride, uint32_t capacity, const uint64_t* __restrict__ sums,
-                    uint64_t* __restrict__ prefix, uint32_t* __restrict__ codes, cts_ms_server_tick* __restrict__ tick,
-                    uint64_t* __restrict__ udp)
-{
-    __shared__ uint64_t wsum[kBlock / 64];
-    __shared__ uint64_t ctr[kBlock / 64][kCounterCount];
-    __shared__ uint32_t red[kBlock / 64][5];
-    zero_counters<kBlock / 64>(ctr);
-    const uint64_t i = (uint64_t)blockIdx.x * kMsServerTile + threadIdx.x;
-    uint32_t code = CTS_MS_SERVER_SENT, c = 0u;
-    uint64_t want = 0;
-    if (i < n) {
-        c = ids[i];
-        want = ms_server_want(servers, c, n_conns, stride, code);
-    }
-    uint64_t total;
-    const uint64_t p = sums[blockIdx.x] + tile_scan_exclusive(want, wsum, total);
-    uint64_t bytes = 0;
-    uint32_t datagrams = 0, sent = 0, finished = 0, no_room = 0, skipped = 0;
-    if (i < n) {
-        prefix[i] = p;
-        if (code != CTS_MS_SERVER_SENT) {
-            skipped = 1u;
-        } else if (p + want > (uint64_t)capacity) {
-            no_room = 1u;
-            code = CTS_MS_SERVER_NO_ROOM;
-        } else {
-            // the only step that knows whether the connection fits is the one that moves its entry
-            cts_ms_server_state* e = servers + c;
-            bytes = e->frame_size_bytes;
-            datagrams = (uint32_t)want;
-            sent = 1u;
-            e->bits_sent += 8u * bytes;
-            e->datagrams_sent += want;
-            const int64_t next = e->current_frame + 1;
-            e->current_frame = next;
-            if (next > e->final_frame) {
-                e->finished = 1u;
-                finished = 1u;
-                code = CTS_MS_SERVER_FINISHED;
-            }
-        }
-        if (codes != nullptr) codes[i] = code;
-    }
-    bytes = wave_sum64(bytes);
-    datagrams = wave_sum(datagrams);
-    sent = wave_sum(sent);
-    finished = wave_sum(finished);
-    no_room = wave_sum(no_room);
-    skipped = wave_sum(skipped);
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 0u) {
-        // the reference's server adds its sent bits to UdpStatusDetails.m_bitsReceived (ctsIOPattern.cpp:1162)
-        ctr[wave][0] = 8u * bytes;                // cts_counters_udp.bits_received
-        ctr[wave][kCounterCount - 1] = datagrams;  // cts_counters_udp.datagrams
-        red[wave][0] = datagrams;
-        red[wave][1] = sent;
-        red[wave][2] = finished;
-        red[wave][3] = no_room;
-        red[wave][4] = skipped;
-    }
-    flush_counters<kBlock / 64>(udp, ctr);  // barrier first
-    if (threadIdx.x < 5u) {
-        uint32_t s = 0;
-#pragma unroll
-        for (int w = 0; w < kBlock / 64; ++w) s += red[w][threadIdx.x];
-        uint32_t* const words = &tick->datagrams;  // datagrams, connections_sent, _finished, _no_room, _skipped
-        if (s) atomicAdd(words + threadIdx.x, s);
-    } else if (threadIdx.x == 5u) {
-        uint64_t s = 0;
-#pragma unroll
-        for (int w = 0; w < kBlock / 64; ++w) s += ctr[w][0];
-        if (s) atomicAdd((unsigned long long*)&tick->bytes, (unsigned long long)(s / 8u));
-    }
-}
+// MediaStream servers on the device (cts_media_stream_servers_send): the ring fill of a tick that cts_tick_plan.hip
+// has planned, with no per-datagram metadata from the host. prefix[i] is listed connection i's first tick-local slot
+// (prefix[n] the total), the tick block holds the datagram count, and the entries have been moved.
 
 // The last i in [lo, hi) with prefix[i] <= g; prefix[lo] <= g.
 __device__ __forceinline__ uint64_t ms_server_listed(const uint64_t* __restrict__ prefix, uint64_t lo, uint64_t hi,
@@ -666,145 +499,11 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // ---------------------------------------------------------------------------------------------
-// TCP senders on the device (cts_tcp_senders_send): one tick of the listed connections' buffer sends with no host
-// descriptor per buffer. Listed connection i wants w_i = min(max_buffers, ceil(R / B)) slots (0 when it sends nothing
-// whatever the room); p_i, the exclusive prefix of the wants in listed order, is its first slot, and it takes
-// t_i = min(w_i, capacity - min(p_i, capacity)) of them. The planning is the servers' three-launch scheme in tiles of
-// kMsServerTile (tcp_sender_sums, ms_server_scan as it stands, tcp_sender_apply); apply also leaves every listed
-// connection's bytes_sent from before the move in the scratch. tcp_sender_descs then writes one descriptor per
-// written slot, and the fill runs over those descriptors with the existing loops (cts_fill_pieces_loop.hpp,
-// cts_fill_team_loop.hpp), its buffer count read from the tick block.
-// Scratch (TcpSenderScratch, cts_internal.hpp): u64 prefix[n + 1], u64 sums[tiles], u64 before[n], a tick.
-static_assert(sizeof(cts_tcp_sender_tick) == sizeof(cts_ms_server_tick), "ms_server_scan zeroes either tick block");
-
-// The slots listed connection c wants, and its code when it sends nothing whatever the room.
-__device__ __forceinline__ uint64_t tcp_sender_want(const cts_tcp_sender_state* __restrict__ senders, uint32_t c,
-                                                    uint32_t n_conns, uint32_t stride, uint32_t max_buffers,
-                                                    uint32_t& code)
-{
-    code = CTS_TCP_SENDER_SKIPPED;
-    if (c >= n_conns) return 0u;
-    const uint32_t B = senders[c].buffer_size;
-    if (B == 0u || B > stride) return 0u;
-    code = CTS_TCP_SENDER_ENDED;
-    const uint64_t sent = senders[c].bytes_sent, transfer = senders[c].transfer_bytes;
-    if (senders[c].finished != 0u || sent >= transfer) return 0u;
-    code = CTS_TCP_SENDER_SENT;
-    const uint64_t R = transfer - sent;
-    const uint64_t k = R / B + (R % B != 0u ? 1u : 0u);
-    return k < max_buffers ? k : max_buffers;
-}
-
-// A wave's 64-bit sum from four 16-bit limbs summed in 32 bits. (Not wave_sum64: with it used here as well,
-// ms_server_sums and ms_server_apply compiled to other instruction text, one 64-bit add's operands swapped)
-__device__ __forceinline__ uint64_t tcp_wave_sum64(uint64_t v)
-{
-    uint64_t s = 0;
-#pragma unroll
-    for (int l = 0; l < 4; ++l) s += (uint64_t)wave_sum((uint32_t)(v >> (16 * l)) & 0xFFFFu) << (16 * l);
-    return s;
-}
-
-__global__ void __launch_bounds__(kBlock)
-    tcp_sender_sums(const uint32_t* __restrict__ ids, uint32_t n, const cts_tcp_sender_state* __restrict__ senders,
-                    uint32_t n_conns, uint32_t stride, uint32_t max_buffers, uint64_t* __restrict__ sums)
-{
-    __shared__ uint64_t wsum[kBlock / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * kMsServerTile + threadIdx.x;
-    uint32_t code;
-    const uint64_t want = i < n ? tcp_sender_want(senders, ids[i], n_conns, stride, max_buffers, code) : 0u;
-    const uint64_t s = tcp_wave_sum64(want);
-    if ((threadIdx.x & 63u) == 0u) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-        uint64_t t = 0;
-#pragma unroll
-        for (int w = 0; w < kBlock / 64; ++w) t += wsum[w];
-        sums[blockIdx.x] = t;
-    }
-}
-
-__global__ void __launch_bounds__(kBlock)
-    tcp_sender_apply(const uint32_t* __restrict__ ids, uint32_t n, cts_tcp_sender_state* __restrict__ senders,
-                     uint32_t n_conns, uint32_t stride, uint32_t capacity, uint32_t max_buffers,
-                     const uint64_t* __restrict__ sums, uint64_t* __restrict__ prefix, uint64_t* __restrict__ before,
-                     uint32_t* __restrict__ codes, cts_tcp_sender_tick* __restrict__ tick, uint64_t* __restrict__ sent_block)
-{
-    __shared__ uint64_t wsum[kBlock / 64];
-    __shared__ uint64_t ctr[kBlock / 64][kCounterCount];
-    __shared__ uint32_t red[kBlock / 64][5];
-    zero_counters<kBlock / 64>(ctr);
-    const uint64_t i = (uint64_t)blockIdx.x * kMsServerTile + threadIdx.x;
-    uint32_t code = CTS_TCP_SENDER_SENT, c = 0u;
-    uint64_t want = 0;
-    if (i < n) {
-        c = ids[i];
-        want = tcp_sender_want(senders, c, n_conns, stride, max_buffers, code);
-    }
-    uint64_t total;
-    const uint64_t p = sums[blockIdx.x] + tile_scan_exclusive(want, wsum, total);
-    uint64_t bytes = 0;
-    uint32_t buffers = 0, sent = 0, finished = 0, no_room = 0, skipped = 0;
-    if (i < n) {
-        prefix[i] = p;
-        const uint64_t pc = p < (uint64_t)capacity ? p : (uint64_t)capacity;
-        const uint64_t t = want < (uint64_t)capacity - pc ? want : (uint64_t)capacity - pc;
-        uint64_t was = 0;
-        if (code != CTS_TCP_SENDER_SENT) {
-            skipped = 1u;
-        } else if (t == 0u) {
-            no_room = 1u;
-            code = CTS_TCP_SENDER_NO_ROOM;
-        } else {
-            // the only step that knows how many slots the connection takes is the one that moves its entry
-            cts_tcp_sender_state* e = senders + c;
-            was = e->bytes_sent;
-            const uint64_t R = e->transfer_bytes - was, full = t * e->buffer_size;  // t <= capacity < 2^32
-            bytes = full < R ? full : R;
-            buffers = (uint32_t)t;
-            sent = 1u;
-            e->bytes_sent = was + bytes;
-            e->buffers_sent += t;
-            if (bytes == R) {
-                e->finished = 1u;
-                finished = 1u;
-                code = CTS_TCP_SENDER_FINISHED;
-            }
-        }
-        before[i] = was;
-        if (codes != nullptr) codes[i] = code;
-    }
-    const uint64_t own_bytes = tcp_wave_sum64(bytes);
-    buffers = wave_sum(buffers);
-    sent = wave_sum(sent);
-    finished = wave_sum(finished);
-    no_room = wave_sum(no_room);
-    skipped = wave_sum(skipped);
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 0u) {
-        ctr[wave][0] = own_bytes;  // cts_counters_sent.bytes_sent (TcpStatusDetails.m_bytesSent, ctsIOPattern.cpp:510)
-        ctr[wave][1] = buffers;    // .buffers_sent
-        ctr[wave][2] = finished;   // .connections_finished
-        red[wave][0] = buffers;
-        red[wave][1] = sent;
-        red[wave][2] = finished;
-        red[wave][3] = no_room;
-        red[wave][4] = skipped;
-    }
-    flush_counters<kBlock / 64>(sent_block, ctr);  // barrier first
-    if (threadIdx.x < 5u) {
-        uint32_t s = 0;
-#pragma unroll
-        for (int w = 0; w < kBlock / 64; ++w) s += red[w][threadIdx.x];
-        uint32_t* const words = &tick->buffers;  // buffers, connections_sent, _finished, _no_room, _skipped
-        if (s) atomicAdd(words + threadIdx.x, s);
-    } else if (threadIdx.x == 5u) {
-        uint64_t s = 0;
-#pragma unroll
-        for (int w = 0; w < kBlock / 64; ++w) s += ctr[w][0];
-        if (s) atomicAdd((unsigned long long*)&tick->bytes, (unsigned long long)s);
-    }
-}
+// TCP senders on the device (cts_tcp_senders_send, cts_tcp_senders_send_paced): what follows a tick's planning
+// (cts_tick_plan.hip), with no host descriptor per buffer. tcp_sender_descs writes one descriptor per written slot from
+// prefix[], before[] (every listed connection's bytes_sent from before the move) and the tick block; the fill runs over
+// those descriptors with the existing loops (cts_fill_pieces_loop.hpp, cts_fill_team_loop.hpp), its buffer count read
+// from the tick block.
 
 // One lane per tick-local slot g < total, grid-stride over the capacity: the descriptor of buffer j = g - prefix[i] of
 // listed connection i, the last one with prefix[i] <= g (prefix[] stays in L2). A launch of its own: at the fill's one
@@ -927,21 +626,6 @@ hipError_t launch_media_stream_fill_strided(uint8_t* arena, uint64_t arena_bytes
     return hipGetLastError();
 }
 
-// cts_media_stream_servers_send's planning: three launches, the middle one a single workgroup
-hipError_t launch_ms_server_plan(const uint32_t* conn_ids, uint32_t n, cts_ms_server_state* servers, uint32_t n_conns,
-                                 uint32_t stride, uint32_t capacity, uint32_t* codes, cts_ms_server_tick* tick,
-                                 uint64_t* udp_counters, const MsServerScratch& scratch, hipStream_t stream)
-{
-    if (n == 0) return hipSuccess;
-    const uint64_t tiles = ms_server_tiles(n);
-    ms_server_sums<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, servers, n_conns, stride, scratch.sums);
-    ms_server_scan<<<1, kBlock, 0, stream>>>(scratch.sums, tiles, scratch.prefix + n,
-                                             reinterpret_cast<uint32_t*>(tick));
-    ms_server_apply<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, servers, n_conns, stride, capacity,
-                                                            scratch.sums, scratch.prefix, codes, tick, udp_counters);
-    return hipGetLastError();
-}
-
 // the tick's ring fill: launch_media_stream_fill_strided's grid rule over the capacity (the total is on the device)
 hipError_t launch_ms_server_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
                                  uint32_t capacity, const uint32_t* conn_ids, uint32_t n,
@@ -966,24 +650,6 @@ hipError_t launch_ms_server_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t 
                 descs, lengths, full_slots, capacity, n_conns);
         },
         geo.fill_nt != 0, stride >= 1024u);
-    return hipGetLastError();
-}
-
-// cts_tcp_senders_send's planning: three launches, the middle one the servers' single-workgroup scan
-hipError_t launch_tcp_sender_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
-                                  cts_tcp_sender_state* senders, uint32_t n_conns, uint32_t stride, uint32_t capacity,
-                                  uint32_t* codes, cts_tcp_sender_tick* tick, uint64_t* sent_counters,
-                                  const TcpSenderScratch& scratch, hipStream_t stream)
-{
-    if (n == 0) return hipSuccess;
-    const uint64_t tiles = ms_server_tiles(n);
-    tcp_sender_sums<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, senders, n_conns, stride, max_buffers,
-                                                            scratch.sums);
-    ms_server_scan<<<1, kBlock, 0, stream>>>(scratch.sums, tiles, scratch.prefix + n,
-                                             reinterpret_cast<uint32_t*>(tick));
-    tcp_sender_apply<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, senders, n_conns, stride, capacity,
-                                                             max_buffers, scratch.sums, scratch.prefix, scratch.before,
-                                                             codes, tick, sent_counters);
     return hipGetLastError();
 }
 

@@ -197,23 +197,26 @@ hipError_t launch_ms_conn_close(const uint32_t* conn_ids, uint32_t n, uint32_t* 
                                 cts_ms_conn_result* results, uint64_t* close_counters, hipStream_t stream,
                                 const LaunchGeometry& geo);
 
-// MediaStream servers on the device (cts_media_stream_servers.cpp). The planning walks the n listed connections in
-// tiles of kMsServerTile; a tick's scratch holds, in this order, the listed connections' exclusive prefix of wanted
-// slots and its grand total (n + 1 words), the tiles' sums, and a tick block for the caller that passes none.
-constexpr uint32_t kMsServerTile = 256;
-inline uint64_t ms_server_tiles(uint32_t n) { return ((uint64_t)n + kMsServerTile - 1) / kMsServerTile; }
+// The device-resident senders' ticks. The planning of all three (the launch_*_plan kernels, cts_tick_plan.hip) walks
+// the n listed connections in tiles of kPlanTile; the fills that follow it are in cts_fill.hip.
+//
+// MediaStream servers on the device (cts_media_stream_servers.cpp). A tick's scratch holds, in this order, the listed
+// connections' exclusive prefix of wanted slots and its grand total (n + 1 words), the tiles' sums, and a tick block
+// for the caller that passes none.
+constexpr uint32_t kPlanTile = 256;
+inline uint64_t plan_tiles(uint32_t n) { return ((uint64_t)n + kPlanTile - 1) / kPlanTile; }
 struct MsServerScratch {
     uint64_t* prefix;           // n + 1
-    uint64_t* sums;             // ms_server_tiles(n)
+    uint64_t* sums;             // plan_tiles(n)
     cts_ms_server_tick* tick;   // 1
     MsServerScratch(void* base, uint32_t n)
         : prefix(static_cast<uint64_t*>(base)), sums(prefix + (uint64_t)n + 1),
-          tick(reinterpret_cast<cts_ms_server_tick*>(sums + ms_server_tiles(n)))
+          tick(reinterpret_cast<cts_ms_server_tick*>(sums + plan_tiles(n)))
     {
     }
     static size_t bytes(uint32_t n)
     {
-        return (size_t)(((uint64_t)n + 1 + ms_server_tiles(n)) * sizeof(uint64_t) + sizeof(cts_ms_server_tick));
+        return (size_t)(((uint64_t)n + 1 + plan_tiles(n)) * sizeof(uint64_t) + sizeof(cts_ms_server_tick));
     }
 };
 // The planning (three launches: tile sums, their scan, apply) writes scratch.prefix, the codes (may be null), `tick`
@@ -235,17 +238,17 @@ hipError_t launch_ms_server_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t 
 // block for the caller that passes none.
 struct TcpSenderScratch {
     uint64_t* prefix;           // n + 1
-    uint64_t* sums;             // ms_server_tiles(n)
+    uint64_t* sums;             // plan_tiles(n)
     uint64_t* before;           // n
     cts_tcp_sender_tick* tick;  // 1
     TcpSenderScratch(void* base, uint32_t n)
-        : prefix(static_cast<uint64_t*>(base)), sums(prefix + (uint64_t)n + 1), before(sums + ms_server_tiles(n)),
+        : prefix(static_cast<uint64_t*>(base)), sums(prefix + (uint64_t)n + 1), before(sums + plan_tiles(n)),
           tick(reinterpret_cast<cts_tcp_sender_tick*>(before + n))
     {
     }
     static size_t bytes(uint32_t n)
     {
-        return (size_t)((2 * (uint64_t)n + 1 + ms_server_tiles(n)) * sizeof(uint64_t) + sizeof(cts_tcp_sender_tick));
+        return (size_t)((2 * (uint64_t)n + 1 + plan_tiles(n)) * sizeof(uint64_t) + sizeof(cts_tcp_sender_tick));
     }
 };
 // The planning (three launches: tile sums, ms_server_scan, apply) writes scratch.prefix and scratch.before, the codes
@@ -264,7 +267,7 @@ hipError_t launch_tcp_sender_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t
                                   const cts_buf_desc* descs, const cts_tcp_sender_tick* tick, hipStream_t stream,
                                   const LaunchGeometry& geo);
 
-// The paced tick (cts_tcp_senders_send_paced; kernels in cts_tcp_paced.hip). Its scratch is the plain tick's with the
+// The paced tick (cts_tcp_senders_send_paced). Its scratch is the plain tick's with the
 // 48-byte tick block at the end, so a TcpSenderScratch over the same base names the same prefix, sums and before,
 // and the descriptor pass and the fill read the paced block's first 32 bytes as the plain tick they expect.
 struct TcpPacedScratch {

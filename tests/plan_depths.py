@@ -24,7 +24,7 @@ import numpy as np
 
 import launch_depths as L
 
-TILE = 256           # listed connections per tile (kMsServerTile)
+TILE = 256           # listed connections per tile (kPlanTile)
 SCAN_BLOCK = 256     # tile sums per pass of ms_server_scan / tcp_paced_scan (kBlock)
 WAVE = 64
 RING_BATCH = L.RING_BATCH
@@ -35,7 +35,8 @@ RING_BPC_DEFAULT, BLOCKS_PER_CU_DEFAULT = 4, 4  # LaunchGeometry's ring_fill_blo
 
 # ---- the planner -----------------------------------------------------------------------------------------------------
 def _wave_sum(wants, defect=None):
-    """tcp_wave_sum64 / tcp_paced_wave_sum64: four 16-bit limbs, each summed over the wave's lanes in 32 bits."""
+    """A wave's exact 64-bit sum by a route of its own: four 16-bit limbs, each summed over the wave's lanes in 32
+    bits. The kernels use wave_sum64."""
     s = 0
     for limb in range(4):
         lanes = sum((v >> (16 * limb)) & 0xFFFF for v in wants)
