@@ -6,13 +6,16 @@
 //   tcp_sender_descs, tcp_sender_fill_pieces / _small   the TCP senders' tick: a descriptor per written slot, then
 //                                     fill_pieces_kernel's or fill_kernel's loop (cts_fill_pieces_loop.hpp,
 //                                     cts_fill_team_loop.hpp) over a count read on the device
-// The slots of both ticks are planned in cts_tick_plan.hip, which writes no pattern byte.
+//   tcp_exchange_descs                the exchange tick (Push, Pull, PushPull, Duplex): a descriptor per written slot
+//                                     by closed form from the buffer's index; the fill is the senders'
+// The slots of the ticks are planned in cts_tick_plan.hip, which writes no pattern byte.
 // The expected chunk is regenerated in registers as in the verify (cts_chunks.hpp); the verify kernels are in
 // cts_verify.hip, the MediaStream receive in cts_media_stream_recv.hip. The alternatives that lost are in DESIGN.md §10.
 #include <hip/hip_runtime.h>
 
 #include "cts_chunks.hpp"
 #include "cts_launch.hpp"
+#include "cts_tcp_exchange_math.hpp"
 
 namespace cts {
 
@@ -560,6 +563,42 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // ---------------------------------------------------------------------------------------------
+// The exchange tick (cts_tcp_exchange_send): tcp_sender_descs over 64-byte entries whose buffers go either way.
+// before[] holds every listed connection's buffers_sent from before the move, so tick-local slot g is element m =
+// before[i] + j of connection ids[i]'s sequence, and its direction, stream position and length are the closed form of
+// cts_tcp_exchange_math.hpp: one 64-bit division (by K, PushPull only) per slot, no loop over buffers or segments.
+// The receiver of direction d is slot c + d x n_conns (n_conns <= 2^31). The fill that follows is the senders'.
+__global__ void __launch_bounds__(kBlock)
+    tcp_exchange_descs(uint32_t stride, uint64_t first_slot, uint32_t capacity, const uint32_t* __restrict__ ids,
+                       uint32_t n, const cts_tcp_exchange_state* __restrict__ entries, uint32_t n_conns,
+                       const uint64_t* __restrict__ prefix, const uint64_t* __restrict__ before,
+                       const cts_tcp_exchange_tick* __restrict__ tick, cts_buf_desc* __restrict__ descs)
+{
+    // (the clamps only matter to a caller who lists a connection twice or passes an entry of its own making: nothing
+    // is written outside the capacity or read outside the table then either, and no descriptor is longer than its
+    // slot)
+    const uint32_t total = tick->tick.buffers < capacity ? tick->tick.buffers : capacity;
+    for (uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x; g < total; g += (uint64_t)gridDim.x * kBlock) {
+        const uint64_t i = ms_server_listed(prefix, 0u, n, g);
+        const uint64_t j = g - prefix[i];
+        const uint32_t c = ids[i];
+        uint32_t len = 0u, off = 0u, receiver = c;
+        if (c < n_conns) {
+            const ExchangeShape S = exchange_shape(entries + c);
+            if (exchange_shape_ok(S)) {
+                uint32_t d;
+                uint64_t pos;
+                exchange_element(S, before[i] + j, d, pos, len);
+                if (len > stride) len = 0u;
+                off = (uint32_t)(pos & 0xFFFFu);
+                receiver = c + d * n_conns;
+            }
+        }
+        descs[g] = cts_buf_desc{(first_slot + g) * stride, len, off, receiver, 0u};
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 static_assert(kGridBlock == (uint32_t)kBlock && kGridFillPiece == kFillPiece && kGridFillBatch == kFillBatch &&
                   kGridRingBatch == kRingBatch,
               "cts_grids.hpp sizes the launches of these kernels");
@@ -663,6 +702,19 @@ hipError_t launch_tcp_sender_descs(uint32_t stride, uint64_t first_slot, uint32_
     const uint32_t grid = grid_for((uint32_t)(((uint64_t)capacity + kBlock - 1) / kBlock), 1, geo);
     tcp_sender_descs<<<grid, kBlock, 0, stream>>>(stride, first_slot, capacity, conn_ids, n, senders, n_conns,
                                                   scratch.prefix, scratch.before, tick, descs);
+    return hipGetLastError();
+}
+
+// the exchange tick's descriptors: launch_tcp_sender_descs' grid
+hipError_t launch_tcp_exchange_descs(uint32_t stride, uint64_t first_slot, uint32_t capacity, const uint32_t* conn_ids,
+                                     uint32_t n, const cts_tcp_exchange_state* entries, uint32_t n_conns,
+                                     const TcpExchangeScratch& scratch, const cts_tcp_exchange_tick* tick,
+                                     cts_buf_desc* descs, hipStream_t stream, const LaunchGeometry& geo)
+{
+    if (n == 0 || capacity == 0) return hipSuccess;
+    const uint32_t grid = grid_for((uint32_t)(((uint64_t)capacity + kBlock - 1) / kBlock), 1, geo);
+    tcp_exchange_descs<<<grid, kBlock, 0, stream>>>(stride, first_slot, capacity, conn_ids, n, entries, n_conns,
+                                                    scratch.plain.prefix, scratch.plain.before, tick, descs);
     return hipGetLastError();
 }
 

@@ -9,6 +9,7 @@
 #include "cts_media_stream.h"
 #include "cts_media_stream_conns.h"
 #include "cts_media_stream_servers.h"
+#include "cts_tcp_exchange.h"
 #include "cts_tcp_senders.h"
 
 namespace cts {
@@ -289,6 +290,54 @@ hipError_t launch_tcp_paced_plan(const uint32_t* conn_ids, uint32_t n, uint32_t 
                                  int64_t now_ms, uint32_t stride, uint32_t capacity, uint32_t* codes,
                                  cts_tcp_sender_paced_tick* tick, uint64_t* sent_counters,
                                  const TcpPacedScratch& scratch, hipStream_t stream);
+
+// The exchange tick (cts_tcp_exchange_send): the senders' scheme over 64-byte entries whose buffers go either way.
+// Its scratch is the plain tick's with `before` holding each listed connection's buffers_sent from before the move
+// and the 48-byte tick block at the end; the fill reads the block's first 32 bytes as the plain tick it expects.
+struct TcpExchangeScratch {
+    TcpSenderScratch plain;
+    cts_tcp_exchange_tick* tick;  // 1
+    TcpExchangeScratch(void* base, uint32_t n)
+        : plain(base, n), tick(reinterpret_cast<cts_tcp_exchange_tick*>(plain.tick))
+    {
+    }
+    static size_t bytes(uint32_t n)
+    {
+        return TcpSenderScratch::bytes(n) - sizeof(cts_tcp_sender_tick) + sizeof(cts_tcp_exchange_tick);
+    }
+};
+// The planning (three launches: tcp_exchange_sums, _scan, _apply) writes what launch_tcp_sender_plan writes, with
+// the tick's bytes by direction; the descriptor pass turns prefix, before and the entries' constants into descs[0 ..
+// tick->tick.buffers) by the closed form of cts_tcp_exchange_math.hpp.
+hipError_t launch_tcp_exchange_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
+                                    cts_tcp_exchange_state* entries, uint32_t n_conns, uint32_t stride,
+                                    uint32_t capacity, uint32_t* codes, cts_tcp_exchange_tick* tick,
+                                    uint64_t* sent_counters, const TcpExchangeScratch& scratch, hipStream_t stream);
+hipError_t launch_tcp_exchange_descs(uint32_t stride, uint64_t first_slot, uint32_t capacity, const uint32_t* conn_ids,
+                                     uint32_t n, const cts_tcp_exchange_state* entries, uint32_t n_conns,
+                                     const TcpExchangeScratch& scratch, const cts_tcp_exchange_tick* tick,
+                                     cts_buf_desc* descs, hipStream_t stream, const LaunchGeometry& geo);
+
+// What the arguments of a TCP tick must satisfy (cts_tcp_senders_send, _send_paced, cts_tcp_exchange_send) once
+// n != 0; dev_entries = the connections' table, need = the scratch size of that tick.
+inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1u)) != 0; }
+inline bool tick_args_ok(const void* dev_arena, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
+                         uint32_t capacity, const uint32_t* dev_conn_ids, uint32_t max_buffers,
+                         const void* dev_entries, uint32_t n_conns, const cts_buf_desc* dev_descs,
+                         const uint32_t* dev_codes, const void* dev_tick, const void* dev_sent_counters,
+                         const void* dev_scratch, size_t scratch_bytes, size_t need)
+{
+    if ((stride & 15u) != 0u || stride < 16u || stride > (16u << 20)) return false;
+    if (max_buffers == 0u) return false;
+    if (dev_arena == nullptr || misaligned(dev_arena, 16)) return false;
+    // (first_slot + capacity) x stride <= arena_bytes, without wrap-around: compared in slots
+    if (first_slot > arena_bytes / stride || (uint64_t)capacity > arena_bytes / stride - first_slot) return false;
+    if (dev_conn_ids == nullptr || misaligned(dev_conn_ids, 4)) return false;
+    if ((n_conns != 0 && dev_entries == nullptr) || misaligned(dev_entries, 8)) return false;
+    if (dev_descs == nullptr || misaligned(dev_descs, 8)) return false;
+    if (misaligned(dev_codes, 4) || misaligned(dev_tick, 8) || misaligned(dev_sent_counters, 8)) return false;
+    return dev_scratch != nullptr && !misaligned(dev_scratch, 8) && scratch_bytes >= need;
+}
 
 // The engine's device and launch geometry for the entry points that live outside cts_engine.cpp (cts_refview.cpp,
 // cts_connections.cpp, cts_media_stream_conns.cpp, cts_media_stream_servers.cpp, cts_tcp_senders.cpp);

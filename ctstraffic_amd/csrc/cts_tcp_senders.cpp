@@ -34,30 +34,12 @@ struct DeviceGuard {
 
 inline int hip_status(hipError_t e) { return e == hipSuccess ? CTS_OK : CTS_E_HIP; }
 
-inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1u)) != 0; }
+using cts::misaligned;
+using cts::tick_args_ok;
 
 inline cts_counters_sent sent_of(const cts_counters_ex& x)
 {
     return cts_counters_sent{x.bytes_checked, x.bytes_ok, x.buffers_checked, {0, 0, 0}};
-}
-
-// What a tick's arguments must satisfy, plain or paced, once n != 0; need = the scratch size of that tick.
-bool tick_args_ok(const void* dev_arena, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
-                  uint32_t capacity, const uint32_t* dev_conn_ids, uint32_t max_buffers,
-                  const cts_tcp_sender_state* dev_senders, uint32_t n_conns, const cts_buf_desc* dev_descs,
-                  const uint32_t* dev_codes, const void* dev_tick, const void* dev_sent_counters,
-                  const void* dev_scratch, size_t scratch_bytes, size_t need)
-{
-    if ((stride & 15u) != 0u || stride < 16u || stride > (16u << 20)) return false;
-    if (max_buffers == 0u) return false;
-    if (dev_arena == nullptr || misaligned(dev_arena, 16)) return false;
-    // (first_slot + capacity) x stride <= arena_bytes, without wrap-around: compared in slots
-    if (first_slot > arena_bytes / stride || (uint64_t)capacity > arena_bytes / stride - first_slot) return false;
-    if (dev_conn_ids == nullptr || misaligned(dev_conn_ids, 4)) return false;
-    if ((n_conns != 0 && dev_senders == nullptr) || misaligned(dev_senders, 8)) return false;
-    if (dev_descs == nullptr || misaligned(dev_descs, 8)) return false;
-    if (misaligned(dev_codes, 4) || misaligned(dev_tick, 8) || misaligned(dev_sent_counters, 8)) return false;
-    return dev_scratch != nullptr && !misaligned(dev_scratch, 8) && scratch_bytes >= need;
 }
 
 }  // namespace

@@ -1,6 +1,6 @@
 // cts_tick_plan.hip — the planning of a device-resident sender's tick for gfx950: which ring slots every listed
-// connection takes, with no pattern byte written. Three senders plan the same way (cts_media_stream_servers_send,
-// cts_tcp_senders_send, cts_tcp_senders_send_paced): listed connection i wants w_i slots (0 when it sends nothing
+// connection takes, with no pattern byte written. Four ticks plan the same way (cts_media_stream_servers_send,
+// cts_tcp_senders_send, cts_tcp_senders_send_paced, cts_tcp_exchange_send): listed connection i wants w_i slots (0 when it sends nothing
 // whatever the room); p_i, the exclusive 64-bit prefix of the wants in listed order, is its first slot, and the room
 // left at p_i decides what it takes. Three plain launches in tiles of kPlanTile listed connections (no workgroup ever
 // waits for another):
@@ -13,6 +13,8 @@
 //   tcp_sender_sums / _apply            the TCP senders (with ms_server_scan: both tick blocks are eight dwords)
 //   tcp_paced_sums / _scan / _apply     the paced TCP senders: the wants cut to what CreateNewTask's send branch
 //                                       (ctsIOPattern.cpp:593-674) lets out at now_ms, from a pace entry per connection
+//   tcp_exchange_sums / _scan / _apply  the exchange tick (cts_tcp_exchange_send): Push, Pull, PushPull and Duplex
+//                                       connections, the wants counted in buffers of a fixed sequence
 // Each step of the scheme is written once here (the tile scan, the tile-sum tail, the scan's passes, the TCP limit, the
 // TCP entry move, the apply tail). What writes the ring from prefix[] is in cts_fill.hip, beside the loops it shares
 // with the other fills.
@@ -22,9 +24,12 @@
 
 #include "cts_chunks.hpp"
 #include "cts_internal.hpp"
+#include "cts_tcp_exchange_math.hpp"
 
 namespace cts {
 
+static_assert(sizeof(cts_tcp_exchange_tick) == 48 && offsetof(cts_tcp_exchange_tick, bytes_dir) == 32,
+              "cts_tcp_exchange_tick: a plain tick and 16 bytes");
 static_assert(kPlanTile == (uint32_t)kBlock, "one listed connection per thread of a tile");
 static_assert(sizeof(cts_tcp_sender_tick) == sizeof(cts_ms_server_tick), "ms_server_scan zeroes either tick block");
 static_assert(sizeof(cts_tcp_sender_pace) == 64 && alignof(cts_tcp_sender_pace) == 8, "cts_tcp_sender_pace: 64 bytes");
@@ -646,6 +651,166 @@ hipError_t launch_tcp_paced_plan(const uint32_t* conn_ids, uint32_t n, uint32_t 
                                                             max_buffers, now_ms, scratch.plain.sums,
                                                             scratch.plain.prefix, scratch.plain.before, codes, tick,
                                                             sent_counters);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// The exchange tick (cts_tcp_exchange_send): Push, Pull, PushPull and Duplex connections from 64-byte entries. Listed
+// connection i wants w_i = min(max_buffers, N - buffers_sent) slots of its buffer sequence and takes t_i as the TCP
+// senders do; whose turn each buffer is follows from its index (cts_tcp_exchange_math.hpp), so the planning never
+// looks at a direction: the move asks the closed form where the entry stands t buffers on.
+//   tcp_exchange_sums    the wants
+//   tcp_exchange_scan    ms_server_scan with the 48-byte tick block zeroed
+//   tcp_exchange_apply   p_i, t_i, the codes, the entries' moves, the tick with its bytes by direction, the sent block
+// apply leaves every listed connection's buffers_sent from before the move in the scratch; tcp_exchange_descs
+// (cts_fill.hip) reads prefix, before and the tick.
+
+namespace {
+
+// The slots listed connection c wants, its code when it sends nothing whatever the room, and of a running connection
+// the entry's constants S and its position m.
+__device__ __forceinline__ uint32_t tcp_exchange_limit(const cts_tcp_exchange_state* __restrict__ entries, uint32_t c,
+                                                       uint32_t n_conns, uint32_t stride, uint32_t max_buffers,
+                                                       uint32_t& code, ExchangeShape& S, uint64_t& m)
+{
+    code = CTS_TCP_SENDER_SKIPPED;
+    m = 0u;
+    if (c >= n_conns) return 0u;
+    S = exchange_shape(entries + c);
+    if (!exchange_shape_ok(S) || S.B > stride) return 0u;
+    code = CTS_TCP_SENDER_ENDED;
+    m = entries[c].buffers_sent;
+    if (entries[c].finished != 0u || m >= S.N) return 0u;
+    code = CTS_TCP_SENDER_SENT;
+    const uint64_t k = S.N - m;
+    return k < (uint64_t)max_buffers ? (uint32_t)k : max_buffers;
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(kBlock)
+    tcp_exchange_sums(const uint32_t* __restrict__ ids, uint32_t n, const cts_tcp_exchange_state* __restrict__ entries,
+                      uint32_t n_conns, uint32_t stride, uint32_t max_buffers, uint64_t* __restrict__ sums)
+{
+    __shared__ uint64_t wsum[kBlock / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
+    uint64_t want = 0;
+    if (i < n) {
+        uint32_t code;
+        ExchangeShape S{};
+        uint64_t m;
+        want = tcp_exchange_limit(entries, ids[i], n_conns, stride, max_buffers, code, S, m);
+    }
+    tile_sum_store(want, wsum, sums);
+}
+
+// One workgroup. tick is 12 dwords (cts_tcp_exchange_tick).
+__global__ void __launch_bounds__(kBlock)
+    tcp_exchange_scan(uint64_t* __restrict__ sums, uint64_t tiles, uint64_t* __restrict__ prefix_total,
+                      uint32_t* __restrict__ tick)
+{
+    __shared__ uint64_t wsum[kBlock / 64];
+    const uint64_t total = tile_sums_scan(sums, tiles, wsum);
+    if (threadIdx.x == 0u) *prefix_total = total;
+    if (threadIdx.x < sizeof(cts_tcp_exchange_tick) / 4u) tick[threadIdx.x] = 0u;
+}
+
+__global__ void __launch_bounds__(kBlock)
+    tcp_exchange_apply(const uint32_t* __restrict__ ids, uint32_t n, cts_tcp_exchange_state* __restrict__ entries,
+                       uint32_t n_conns, uint32_t stride, uint32_t capacity, uint32_t max_buffers,
+                       const uint64_t* __restrict__ sums, uint64_t* __restrict__ prefix, uint64_t* __restrict__ before,
+                       uint32_t* __restrict__ codes, cts_tcp_exchange_tick* __restrict__ tick,
+                       uint64_t* __restrict__ sent_block)
+{
+    __shared__ uint64_t wsum[kBlock / 64];
+    __shared__ uint64_t ctr[kBlock / 64][kCounterCount];
+    __shared__ uint32_t red[kBlock / 64][5];
+    __shared__ uint64_t dir[kBlock / 64][2];
+    zero_counters<kBlock / 64>(ctr);
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
+    uint32_t code = CTS_TCP_SENDER_SENT, c = 0u;
+    uint64_t want = 0, m = 0;
+    ExchangeShape S{};
+    if (i < n) {
+        c = ids[i];
+        want = tcp_exchange_limit(entries, c, n_conns, stride, max_buffers, code, S, m);
+    }
+    uint64_t total;
+    const uint64_t p = sums[blockIdx.x] + tile_scan_exclusive(want, wsum, total);
+    uint64_t bytes0 = 0, bytes1 = 0;
+    uint32_t buffers = 0, sent = 0, finished = 0, no_room = 0, skipped = 0;
+    if (i < n) {
+        prefix[i] = p;
+        const uint64_t pc = p < (uint64_t)capacity ? p : (uint64_t)capacity;
+        const uint64_t t = want < (uint64_t)capacity - pc ? want : (uint64_t)capacity - pc;
+        if (code != CTS_TCP_SENDER_SENT) {
+            skipped = 1u;
+        } else if (t == 0u) {
+            no_room = 1u;
+            code = CTS_TCP_SENDER_NO_ROOM;
+        } else {
+            // the only step that knows how many slots a connection takes is the one that moves its entry: the bytes
+            // of buffers m .. m + t by direction are the difference of two positions, whatever segment ends lie
+            // between, and the entry holds the position at m (cts_tcp_exchange_init, _seek and this move keep it so)
+            cts_tcp_exchange_state* const e = entries + c;
+            uint64_t to[2];
+            exchange_position(S, m + t, to);
+            bytes0 = exchange_sub(to[0], e->bytes_sent[0]);
+            bytes1 = exchange_sub(to[1], e->bytes_sent[1]);
+            e->bytes_sent[0] += bytes0;
+            e->bytes_sent[1] += bytes1;
+            e->buffers_sent = m + t;
+            buffers = (uint32_t)t;
+            sent = 1u;
+            if (m + t == S.N) {
+                e->finished = 1u;
+                finished = 1u;
+                code = CTS_TCP_SENDER_FINISHED;
+            }
+        }
+        before[i] = m;
+        if (codes != nullptr) codes[i] = code;
+    }
+    bytes0 = wave_sum64(bytes0);
+    bytes1 = wave_sum64(bytes1);
+    const uint64_t bytes = bytes0 + bytes1;
+    // buffers, connections_sent, _finished, _no_room, _skipped
+    const uint32_t words[5] = {wave_sum(buffers), wave_sum(sent), wave_sum(finished), wave_sum(no_room),
+                               wave_sum(skipped)};
+    if ((threadIdx.x & 63u) == 0u) {
+        uint64_t* const own = ctr[threadIdx.x >> 6];
+        own[0] = bytes;     // cts_counters_sent.bytes_sent (TcpStatusDetails.m_bytesSent of whichever side sent)
+        own[1] = words[0];  // .buffers_sent
+        own[2] = words[2];  // .connections_finished
+        dir[threadIdx.x >> 6][0] = bytes0;
+        dir[threadIdx.x >> 6][1] = bytes1;
+    }
+    apply_flush(words, bytes, red, wsum, ctr, sent_block, [&](uint32_t k) { return &tick->tick.buffers + k; },
+                &tick->tick.bytes);
+    if (threadIdx.x >= 8u && threadIdx.x < 10u) {
+        const uint32_t d = threadIdx.x - 8u;
+        uint64_t s = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) s += dir[w][d];
+        if (s) atomicAdd((unsigned long long*)&tick->bytes_dir[d], (unsigned long long)s);
+    }
+}
+
+// cts_tcp_exchange_send's planning: three launches, the middle one a single workgroup
+hipError_t launch_tcp_exchange_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
+                                    cts_tcp_exchange_state* entries, uint32_t n_conns, uint32_t stride,
+                                    uint32_t capacity, uint32_t* codes, cts_tcp_exchange_tick* tick,
+                                    uint64_t* sent_counters, const TcpExchangeScratch& scratch, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    const uint64_t tiles = plan_tiles(n);
+    tcp_exchange_sums<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, entries, n_conns, stride, max_buffers,
+                                                              scratch.plain.sums);
+    tcp_exchange_scan<<<1, kBlock, 0, stream>>>(scratch.plain.sums, tiles, scratch.plain.prefix + n,
+                                                reinterpret_cast<uint32_t*>(tick));
+    tcp_exchange_apply<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, entries, n_conns, stride, capacity,
+                                                               max_buffers, scratch.plain.sums, scratch.plain.prefix,
+                                                               scratch.plain.before, codes, tick, sent_counters);
     return hipGetLastError();
 }
 

@@ -207,3 +207,22 @@ TCP_SENDER_PACED_TICK_DTYPE = np.dtype(
 TCP_SENDER_WAITING = 5
 TCP_SENDER_NO_DUE = (1 << 63) - 1  # next_due_ms when nothing is pending
 assert TCP_SENDER_PACE_DTYPE.itemsize == 64 and TCP_SENDER_PACED_TICK_DTYPE.itemsize == 48
+# cts_tcp_exchange_state (include/cts_tcp_exchange.h): one Push, Pull, PushPull or Duplex connection's device entry
+TCP_EXCHANGE_DTYPE = np.dtype(
+    [
+        ("transfer_bytes", "<u8"),
+        ("total_buffers", "<u8"),
+        ("buffers_sent", "<u8"),
+        ("bytes_sent", "<u8", (2,)),
+        ("buffer_size", "<u4"),
+        ("pattern", "<u4"),
+        ("push_bytes", "<u4"),
+        ("pull_bytes", "<u4"),
+        ("finished", "<u4"),
+        ("reserved", "<u4"),
+    ]
+)
+TCP_EXCHANGE_PUSH, TCP_EXCHANGE_PULL, TCP_EXCHANGE_PUSHPULL, TCP_EXCHANGE_DUPLEX = 0, 1, 2, 3
+# cts_tcp_exchange_tick: what one cts_tcp_exchange_send did; its first 32 bytes are a cts_tcp_sender_tick
+TCP_EXCHANGE_TICK_DTYPE = np.dtype(TCP_SENDER_TICK_DTYPE.descr + [("bytes_dir", "<u8", (2,))])
+assert TCP_EXCHANGE_DTYPE.itemsize == 64 and TCP_EXCHANGE_TICK_DTYPE.itemsize == 48

@@ -1103,3 +1103,241 @@ def tcp_paced_sender_view(entries: np.ndarray, pace: np.ndarray, now_ms: int, st
             "connections_pending": len(due)}
     return TcpPacedSenderTickView(v.arena, v.descs, v.codes, v.tick, v.counters, v.entries, v.prefix, v.taken,
                                   q_out, np.nonzero(v.codes == 5)[0], tail, wanted)
+
+
+# ---- Push, Pull, PushPull and Duplex on the device-resident path (include/cts_tcp_exchange.h) ----------------------
+TCP_EXCHANGE_TICK_FIELDS = TCP_SENDER_TICK_FIELDS + ("bytes_dir",)
+
+
+def tcp_exchange_sequence(pattern: int, transfer: int, B: int, P: int = 0, Q: int = 0):
+    """A connection's buffers one step at a time, as the reference's patterns hand them out: a restatement of
+    GetNextTaskFromPattern / CompleteTaskBackToPattern (ctsIOPattern.cpp:808-1099) with every task completed in full
+    before the next is asked for, and for Duplex the two directions taking turns, direction 0 first. Yields (direction,
+    stream position, length, m_intraSegmentTransfer before the buffer). Kept apart from the closed form
+    (tcp_exchange_element): this one walks, that one jumps."""
+    from .types import TCP_EXCHANGE_DUPLEX, TCP_EXCHANGE_PULL, TCP_EXCHANGE_PUSH, TCP_EXCHANGE_PUSHPULL
+
+    sent = [0, 0]
+    if pattern in (TCP_EXCHANGE_PUSH, TCP_EXCHANGE_PULL):
+        d, remaining = (0 if pattern == TCP_EXCHANGE_PUSH else 1), transfer
+        while remaining:
+            n = min(B, remaining)  # CreateNewTask: min(remaining transfer, buffer size)
+            yield d, sent[d], n, 0
+            sent[d] += n
+            remaining -= n
+    elif pattern == TCP_EXCHANGE_PUSHPULL:
+        sending, intra, remaining = True, 0, transfer  # the client's m_sending: clients start sending
+        while remaining:
+            segment = P if sending else Q
+            assert intra < segment
+            n = min(B, remaining, segment - intra)  # CreateTrackedTask(action, segmentSize - m_intraSegmentTransfer)
+            d = 0 if sending else 1
+            yield d, sent[d], n, intra
+            sent[d] += n
+            remaining -= n
+            intra += n
+            if intra == segment:
+                sending, intra = not sending, 0
+    elif pattern == TCP_EXCHANGE_DUPLEX:
+        transfer += transfer % 2  # max transfer bytes must be even
+        left = [transfer // 2, transfer // 2]  # m_remainingSendBytes of the two sides
+        d = 0
+        while left[0] or left[1]:
+            if left[d]:
+                n = min(B, left[d])
+                yield d, sent[d], n, 0
+                sent[d] += n
+                left[d] -= n
+            d ^= 1
+    else:
+        raise ValueError("pattern %d" % pattern)
+
+
+def tcp_exchange_total_buffers(pattern: int, transfer: int, B: int, P: int = 0, Q: int = 0) -> int:
+    """N of include/cts_tcp_exchange.h, in Python integers."""
+    if pattern in (0, 1):
+        return -(-transfer // B)
+    if pattern == 3:
+        return 2 * -(-((transfer + transfer % 2) // 2) // B)
+    kp, kq, C = -(-P // B), -(-Q // B), P + Q
+    rem = transfer % C
+    return transfer // C * (kp + kq) + (-(-rem // B) if rem <= P else kp + -(-(rem - P) // B))
+
+
+def tcp_exchange_element(pattern: int, transfer: int, B: int, P: int, Q: int, m: int):
+    """Element m of the sequence by the closed form of include/cts_tcp_exchange.h, in Python integers: (direction,
+    stream position, length, m_intraSegmentTransfer)."""
+    if pattern in (0, 1):
+        return pattern, m * B, min(B, transfer - m * B), 0
+    if pattern == 3:
+        H = (transfer + transfer % 2) // 2
+        return m & 1, (m >> 1) * B, min(B, H - (m >> 1) * B), 0
+    kp, kq, C = -(-P // B), -(-Q // B), P + Q
+    y, r = divmod(m, kp + kq)
+    if r < kp:
+        s = r * B
+        return 0, y * P + s, min(B, P - s, transfer - (y * C + s)), s
+    s = (r - kp) * B
+    return 1, y * Q + s, min(B, Q - s, transfer - (y * C + P + s)), s
+
+
+def tcp_exchange_position(pattern: int, transfer: int, B: int, P: int, Q: int, m: int):
+    """[bytes of direction 0, of direction 1] that the first m <= N buffers carry, by closed form."""
+    if m >= tcp_exchange_total_buffers(pattern, transfer, B, P, Q):
+        if pattern in (0, 1):
+            return [transfer * (1 - pattern), transfer * pattern]
+        if pattern == 3:
+            return [(transfer + transfer % 2) // 2] * 2
+        full, rem = divmod(transfer, P + Q)
+        return [full * P + min(rem, P), full * Q + max(rem - P, 0)]
+    d, pos, _, _ = tcp_exchange_element(pattern, transfer, B, P, Q, m)
+    # buffer m is the next of direction d at pos; the other direction stands where its next buffer starts
+    if pattern in (0, 1):
+        other = 0
+    elif pattern == 3:
+        other = min((m + 1) // 2 * B, (transfer + transfer % 2) // 2) if d == 1 else pos
+    else:
+        y = m // (-(-P // B) + -(-Q // B))
+        other = y * P + P if d == 1 else y * Q
+    return [pos, other] if d == 0 else [other, pos]
+
+
+def tcp_exchange_entries(settings, seek=None):
+    """cts_tcp_exchange_init (and, with seek = a position per connection, cts_tcp_exchange_seek) as a model, for a list
+    of (pattern, transfer_bytes, buffer_size[, push_bytes, pull_bytes]). Returns TCP_EXCHANGE_DTYPE[len(settings)];
+    raises ValueError where the C functions return CTS_E_INVALID."""
+    from .types import TCP_EXCHANGE_DTYPE
+
+    e = np.zeros(len(settings), dtype=TCP_EXCHANGE_DTYPE)
+    for c, s in enumerate(settings):
+        pattern, transfer, B = s[:3]
+        P, Q = (tuple(s[3:5]) + (0, 0))[:2]
+        bad = (transfer <= 0 or B <= 0 or transfer >= 1 << 64 or B >= 1 << 32 or pattern not in (0, 1, 2, 3)
+               or not 0 <= P < 1 << 32 or not 0 <= Q < 1 << 32 or (pattern == 2 and (P == 0 or Q == 0))
+               or (pattern == 3 and transfer == (1 << 64) - 1))
+        if bad:
+            raise ValueError("connection %d: pattern %d, transfer %d, buffer size %d, segments %d and %d"
+                             % (c, pattern, transfer, B, P, Q))
+        if pattern == 3:
+            transfer += transfer % 2
+        N = tcp_exchange_total_buffers(pattern, transfer, B, P, Q)
+        m = 0 if seek is None else int(seek[c])
+        if not 0 <= m <= N:
+            raise ValueError("connection %d: position %d of %d" % (c, m, N))
+        e[c] = (transfer, N, m, tcp_exchange_position(pattern, transfer, B, P, Q, m), B, pattern, P, Q, int(m == N), 0)
+    return e
+
+
+def _exchange_elements(e, m):
+    """tcp_exchange_element over arrays: e = TCP_EXCHANGE_DTYPE records (one per buffer), m = their indices (uint64).
+    Returns (direction, stream position, length) as uint64 arrays."""
+    u = np.uint64
+    T, B = e["transfer_bytes"].astype(u), e["buffer_size"].astype(u)
+    P, Q, pattern = e["push_bytes"].astype(u), e["pull_bytes"].astype(u), e["pattern"]
+    one = u(1)
+    sub = lambda a, b: np.where(a > b, a - b, u(0))  # noqa: E731
+    # Push, Pull
+    d = np.where(pattern == 1, one, u(0))
+    pos = m * B
+    length = np.minimum(B, sub(T, pos))
+    # Duplex
+    dup = pattern == 3
+    H = T // u(2) + (T & one)
+    pos_d = (m >> one) * B
+    d = np.where(dup, m & one, d)
+    pos = np.where(dup, pos_d, pos)
+    length = np.where(dup, np.minimum(B, sub(H, pos_d)), length)
+    # PushPull
+    pp = pattern == 2
+    Bs = np.where(B == 0, one, B)
+    kp, kq = (P + Bs - one) // Bs, (Q + Bs - one) // Bs
+    K = np.where(kp + kq == 0, one, kp + kq)
+    y = m // K
+    r = m - y * K
+    push = r < kp
+    s = np.where(push, r, r - np.minimum(kp, r)) * B
+    seg = np.where(push, P, Q)
+    G = y * (P + Q) + np.where(push, u(0), P) + s
+    d = np.where(pp, np.where(push, u(0), one), d)
+    pos = np.where(pp, y * seg + s, pos)
+    length = np.where(pp, np.minimum(np.minimum(B, sub(seg, s)), sub(T, G)), length)
+    return d, pos, length
+
+
+@dataclass
+class TcpExchangeTickView:
+    """What one cts_tcp_exchange_send leaves behind (tcp_exchange_view)."""
+    arena: np.ndarray     # the arena's bytes after the tick
+    descs: np.ndarray     # DESC_DTYPE[capacity]: [0, total) the tick's, the rest as before
+    codes: np.ndarray     # uint32 per listed id
+    tick: dict            # TCP_EXCHANGE_TICK_FIELDS (bytes_dir a list of two)
+    counters: dict        # SENT_FIELDS: the sent block after the tick
+    entries: np.ndarray   # TCP_EXCHANGE_DTYPE after the tick
+    prefix: np.ndarray    # uint64 per listed id: its first tick-local slot
+    taken: np.ndarray     # uint64 per listed id: the slots it took
+    direction: np.ndarray  # uint64 per written buffer
+
+
+def tcp_exchange_view(entries: np.ndarray, stride: int, arena: np.ndarray, first_slot: int, capacity: int, ids,
+                      max_buffers: int, descs: np.ndarray = None, counters: dict = None) -> TcpExchangeTickView:
+    """One tick of cts_tcp_exchange_send as a model, in numpy closed forms over the listed connections and over the
+    tick's buffers (the only Python loop runs over the distinct buffer lengths). arena, descs (what dev_descs held
+    before, default zeros) and counters (the sent block before, default zeros) are not modified; the results are
+    copies."""
+    from .types import TCP_EXCHANGE_DTYPE
+
+    u = np.uint64
+    e = np.array(entries, dtype=TCP_EXCHANGE_DTYPE, copy=True)
+    ids = np.array([int(x) for x in ids], dtype=u)
+    n, n_conns = len(ids), len(e)
+    table = e if n_conns else np.zeros(1, dtype=TCP_EXCHANGE_DTYPE)
+    valid = ids < u(n_conns)
+    c = np.where(valid, ids, u(0)).astype(np.int64)
+    E = table[c]
+    B, N, m0 = E["buffer_size"].astype(u), E["total_buffers"].astype(u), E["buffers_sent"].astype(u)
+    malformed = (B == 0) | (E["pattern"] > 3) | ((E["pattern"] == 2) & ((E["push_bytes"] == 0) | (E["pull_bytes"] == 0)))
+    skipped = ~valid | malformed | (B > u(stride))
+    ended = ~skipped & ((E["finished"] != 0) | (m0 >= N))
+    running = ~skipped & ~ended
+    w = np.where(running, np.minimum(N - np.minimum(m0, N), u(max_buffers)), u(0))
+    p = np.concatenate([np.zeros(1, dtype=u), np.cumsum(w, dtype=u)])[:n]
+    cap = u(capacity)
+    t = np.minimum(w, cap - np.minimum(p, cap))
+    took = running & (t > 0)
+    finished = took & (m0 + t == N)
+    codes = np.zeros(n, dtype=np.uint32)
+    codes[skipped], codes[ended], codes[running & (t == 0)], codes[finished] = 4, 2, 3, 1
+    total = int(t.sum())
+    # the buffers: listed connection `owner` of tick-local slot g, its buffer j, element m of its sequence
+    owner = np.repeat(np.arange(n, dtype=np.int64), t.astype(np.int64))
+    g = np.arange(total, dtype=u)
+    m = m0[owner] + (g - p[owner])
+    d, pos, length = _exchange_elements(E[owner], m)
+    offset = pos & u(PATTERN_PERIOD - 1)
+    by_dir = [int(length[d == u(k)].sum()) for k in (0, 1)]
+    tick = {"bytes": sum(by_dir), "buffers": total, "connections_sent": int(took.sum()),
+            "connections_finished": int(finished.sum()), "connections_no_room": int((running & (t == 0)).sum()),
+            "connections_skipped": int((skipped | ended).sum()), "bytes_dir": by_dir}
+    out_descs = np.zeros(capacity, dtype=DESC_DTYPE) if descs is None else np.array(descs, dtype=DESC_DTYPE, copy=True)
+    dd = out_descs[:total]
+    dd["byte_offset"] = (u(first_slot) + g) * u(stride)
+    dd["length"], dd["expected_pattern_offset"], dd["skip_head"] = length, offset, 0
+    dd["conn_index"] = ids[owner] + d * u(n_conns)
+    out = np.array(arena, dtype=np.uint8, copy=True)
+    rows = out[: len(out) // stride * stride].reshape(-1, stride)
+    P = _pattern_prefix(PATTERN_PERIOD)
+    for L in np.unique(length):
+        L = int(L)
+        mine = np.nonzero(length == u(L))[0]
+        tiled = np.tile(P, (PATTERN_PERIOD + L - 1) // PATTERN_PERIOD + 1)[: PATTERN_PERIOD + L - 1]
+        windows = np.lib.stride_tricks.sliding_window_view(tiled, L)
+        rows[first_slot + mine, :L] = windows[offset[mine].astype(np.int64)]
+    for k in (0, 1):
+        np.add.at(e["bytes_sent"][:, k], c[owner][d == u(k)], length[d == u(k)])
+    e["buffers_sent"][c[took]] = m0[took] + t[took]
+    e["finished"][c[finished]] = 1
+    after = dict.fromkeys(SENT_FIELDS, 0) if counters is None else dict(counters)
+    after["bytes_sent"] += tick["bytes"]
+    after["buffers_sent"] += total
+    after["connections_finished"] += tick["connections_finished"]
+    return TcpExchangeTickView(out, out_descs, codes, tick, after, e, p, t, d)
