@@ -516,7 +516,9 @@ class TickPlan:
     first_slot = seam // stride - 3, the second at first_slot + what the first one wrote.
 
     kind "server": cts_media_stream_servers_send; "tcp": cts_tcp_senders_send; "paced": cts_tcp_senders_send_paced,
-    with pace "cut" (a rate limit stops two connections in the tick) or "unpaced".
+    with pace "cut" (a rate limit stops two connections in the tick) or "unpaced"; "exchange":
+    cts_tcp_exchange_send over a Push, a Pull, two PushPull (one seeked far out, so that its push-to-pull turn falls
+    inside the first tick), a Duplex connection and one that finds no room.
 
     The expected state comes from the models of ctstraffic_amd.workload, run at the rebased first slot 1 over a host
     arena that starts one slot below the first tick; rebase=False runs them at the true first slot over a host arena
@@ -535,6 +537,16 @@ class TickPlan:
             self.ids = [3, 1, 0, 2, 4]          # slot 3 of the first tick is a full datagram of connection 0
             self.capacity = 12                  # 1 + 1 + 4 + 3, connection 4 finds no room
             self.entries = W.media_stream_server_entries(self.settings)
+        elif kind == "exchange":
+            B = self.B
+            Pb, Qb = 2 * B + B // 2, B + 1      # a cycle is the buffers B, B, B // 2 | B, 1
+            self.settings = [(0, 8 * B, B), (1, 3 * B + 1, B), (2, 1 << 60, B, Pb, Qb), (2, 20 * B + 7, B, Pb, Qb),
+                             (3, 5 * B + 3, B), (0, 6 * B, B)]
+            self.seek = [0, 0, 5 * ((1 << 33) // 5 + 1) + 1, 0, 0, 0]   # buffers B, B // 2 | B of a cycle far out
+            self.ids = [2, 0, 4, 1, 3, 5]
+            self.max_buffers = 3
+            self.capacity = 14                  # 3 + 3 + 3 + 3 + 2 of 3, connection 5 finds no room
+            self.entries = W.tcp_exchange_entries(self.settings, seek=self.seek)
         else:
             B = self.B
             self.settings = [(3 * B + 1, B), (8 * B, B), (2 * B + B // 2 + 1, B), (1 << 40, B), (1, B), (6 * B, B)]
@@ -574,12 +586,15 @@ class TickPlan:
                                 host=view.ring.copy()))
                 first += n
         else:
-            entries, pace, counters = self.entries, self.pace, None
+            entries, pace, counters = self.entries, getattr(self, "pace", None), None
             descs, left = np.zeros(self.capacity, DESC_DTYPE), np.zeros(self.capacity, DESC_DTYPE)
             for t in range(TICKS):
                 if self.kind == "tcp":
                     v = W.tcp_sender_view(entries, s, host, first - self.base_slot, self.capacity, self.ids,
                                           self.max_buffers, descs=descs, counters=counters)
+                elif self.kind == "exchange":
+                    v = W.tcp_exchange_view(entries, s, host, first - self.base_slot, self.capacity, self.ids,
+                                            self.max_buffers, descs=descs, counters=counters)
                 else:
                     v = W.tcp_paced_sender_view(entries, pace, self.now[t], s, host, first - self.base_slot,
                                                 self.capacity, self.ids, self.max_buffers, descs=descs,
@@ -590,8 +605,8 @@ class TickPlan:
                 left["byte_offset"][:n] += np.uint64(shift)
                 out.append(dict(first_slot=first, written=n, descs=left.copy(), codes=v.codes.copy(),
                                 tick=dict(v.tick), entries=entries.copy(), counters=dict(counters), host=host,
-                                pace=None if self.kind == "tcp" else pace.copy(),
-                                tail=None if self.kind == "tcp" else dict(v.tail)))
+                                pace=pace.copy() if self.kind == "paced" else None,
+                                tail=dict(v.tail) if self.kind == "paced" else None))
                 first += n
         self._ticks = out
         return out
@@ -642,3 +657,17 @@ class TickPlan:
             if off + length > max(self.seam, off + head):
                 return 0, g, max(self.seam, off + head)
         raise AssertionError("no slot above the seam")
+
+
+# ---- one exchange tick that moves more than 4 GiB -------------------------------------------------------------------
+BIG_STRIDE = 16 << 20  # the largest stride a tick takes
+
+
+def big_exchange_tick() -> dict:
+    """One cts_tcp_exchange_send whose bytes need more than 32 bits: stride 16 MiB, B = 16 MiB - 5, four PushPull
+    connections of P = 3B, Q = B that take 86 buffers each (21 cycles and two more push buffers: 65 of direction 0,
+    21 of direction 1) and a Duplex one that takes the 16 slots left of a capacity of 360. Direction 0 carries 268
+    buffers, 2^32 bytes and more; the slot that starts at byte 2^32 of the arena is slot 256."""
+    B = BIG_STRIDE - 5
+    return {"stride": BIG_STRIDE, "B": B, "settings": [(2, 1 << 40, B, 3 * B, B)] * 4 + [(3, 1 << 40, B)],
+            "ids": [0, 1, 2, 3, 4], "max_buffers": 86, "capacity": 360}

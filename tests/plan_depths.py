@@ -17,6 +17,12 @@ of its paths a tick reaches before it compares a device result:
 The grid rules are tests/launch_depths.py's (held against cts_grids.hpp there). The numpy models of
 ctstraffic_amd/workload.py are the reference for outcomes and are not called here. The cases of the two test files
 live here too.
+
+The exchange tick (cts_tcp_exchange_send: tcp_exchange_sums / _scan / _apply and tcp_exchange_descs) plans the same
+way and has its cases at the end: long_exchange, idle_runs("exchange", ...) and wide_exchange. Its reference is
+exchange_tick, the whole tick one listed connection at a time in Python integers (buffers from
+workload.tcp_exchange_element, positions from workload.tcp_exchange_position, never the numpy model), which
+tests/exchange_edges.py uses as well.
 """
 import bisect
 
@@ -491,26 +497,30 @@ IDLE_RUNS = (511, 512, 513, 1500)
 S_SLOTS = 3
 
 
-def idle_run_tokens(lead, total, filler):
+def idle_run_tokens(lead, total, filler, kinds=3):
     """The list of case B as tokens ("send", slots) and ("idle", kind): fillers that send `lead` slots in all, then
-    [S, idle x 511, S, idle x 512, S, idle x 513, S, idle x 1500, S, S, idle x 700] with S sending 3 and the idle
-    kinds taking turns, then fillers up to `total` slots. A filler sends `filler` slots, the last of a stretch less."""
+    [S, idle x 511, S, idle x 512, S, idle x 513, S, idle x 1500, S, S, idle x 700] with S sending 3 and the `kinds`
+    idle kinds taking turns, then fillers up to `total` slots. A filler sends `filler` slots, the last of a stretch
+    less."""
     def fill(slots):
         return [("send", filler)] * (slots // filler) + ([("send", slots % filler)] if slots % filler else [])
 
     out, kind = fill(lead), 0
     for run in IDLE_RUNS:
         out.append(("send", S_SLOTS))
-        out += [("idle", (kind + j) % 3) for j in range(run)]
+        out += [("idle", (kind + j) % kinds) for j in range(run)]
         kind += run
-    out += [("send", S_SLOTS), ("send", S_SLOTS)] + [("idle", j % 3) for j in range(700)]
+    out += [("send", S_SLOTS), ("send", S_SLOTS)] + [("idle", j % kinds) for j in range(700)]
     return out + fill(total - lead - 6 * S_SLOTS)
 
 
 def idle_runs(kind, stride, lead=0, total=6 * S_SLOTS + 170 * S_SLOTS, filler=S_SLOTS):
     """Case B: settings, ids and wants of idle_run_tokens. kind "ms": M = 53 at stride 64 and 1040 at 1040, a frame of
     `slots` datagrams, its last one short on every second connection. kind "tcp": B = stride - 3, max_buffers 3. The
-    idle kinds: a finished connection, an id beyond the table, a datagram (or buffer) size above the stride."""
+    idle kinds: a finished connection, an id beyond the table, a datagram (or buffer) size above the stride. kind
+    "exchange": see _idle_runs_exchange."""
+    if kind == "exchange":
+        return _idle_runs_exchange(stride, lead, total, filler)
     tokens = idle_run_tokens(lead, total, filler)
     settings, finished, ids, w = [], [], [], []
     beyond = 0
@@ -643,3 +653,247 @@ def wide_ms():
     settings = [(100, 53, 3) if k == "s" else (HUGE_FRAME, MIN_DATAGRAM, 3) for k in kinds]
     return {"settings": settings, "finished": (), "ids": list(range(len(kinds))), "stride": 64, "capacity": 64,
             "kinds": kinds}
+
+
+# ---- the exchange tick (cts_tcp_exchange_send): Push, Pull, PushPull and Duplex --------------------------------------
+# A connection is a list [pattern, T, B, P, Q, N, m, bytes of direction 0, of direction 1, finished] of Python integers.
+XP, XT, XB, XPUSH, XPULL, XN, XM, XS0, XS1, XFIN = range(10)
+PUSH, PULL, PUSHPULL, DUPLEX = range(4)
+X_DEFECTS = ("kp32", "c32", "k32", "m48", "n32")
+M48 = (1 << 48) - 1
+
+
+def exchange_state(settings, seek=None, finished=(), pattern4=(), no_push=()):
+    """The entries of cts_tcp_exchange_init (seek: then moved to that position) for (pattern, T, B[, P, Q]) settings.
+    finished, pattern4, no_push: entries overwritten afterwards as finished, with pattern 4, with push_bytes 0."""
+    from ctstraffic_amd import workload as W
+
+    state = []
+    for c, s in enumerate(settings):
+        pattern, T, B = s[:3]
+        Pb, Qb = (tuple(s[3:5]) + (0, 0))[:2]
+        if pattern == DUPLEX:
+            T += T % 2
+        N = W.tcp_exchange_total_buffers(pattern, T, B, Pb, Qb)
+        m = 0 if seek is None else int(seek[c])
+        assert 0 <= m <= N, (c, m, N)
+        s0, s1 = W.tcp_exchange_position(pattern, T, B, Pb, Qb, m)
+        state.append([pattern, T, B, Pb, Qb, N, m, s0, s1, int(m == N)])
+    for c in finished:
+        state[c][XFIN] = 1
+    for c in pattern4:
+        state[c][XP] = 4
+    for c in no_push:
+        state[c][XPUSH] = 0
+    return state
+
+
+def exchange_case_state(case):
+    return exchange_state(case["settings"], case.get("seek"), case.get("finished", ()), case.get("pattern4", ()),
+                          case.get("no_push", ()))
+
+
+def exchange_records(state):
+    """state as TCP_EXCHANGE_DTYPE records."""
+    from ctstraffic_amd.types import TCP_EXCHANGE_DTYPE
+
+    out = np.zeros(len(state), dtype=TCP_EXCHANGE_DTYPE)
+    for c, e in enumerate(state):
+        out[c] = (e[XT], e[XN], e[XM], [e[XS0], e[XS1]], e[XB], e[XP], e[XPUSH], e[XPULL], e[XFIN], 0)
+    return out
+
+
+def _pushpull_counts(e, defect):
+    """(kp, kq, K, the division's K, C) as a device build with that defect would hold them."""
+    B, Pb, Qb = e[XB], e[XPUSH], e[XPULL]
+    cut = M32 if defect == "kp32" else M64
+    kp, kq = ((Pb + B - 1) & cut) // B, ((Qb + B - 1) & cut) // B
+    K = kp + kq
+    divisor = (K & M32) or 1 if defect == "k32" else K or 1
+    return kp, kq, K, divisor, (Pb + Qb) & (M32 if defect == "c32" else M64)
+
+
+def _exchange_element(e, m, defect=None):
+    """(direction, stream position, length) of element m: workload.tcp_exchange_element, or with an X_DEFECTS defect
+    what exchange_element of cts_tcp_exchange_math.hpp would give were that one quantity cut short (modulo 2^64,
+    subtractions saturating, as there)."""
+    from ctstraffic_amd import workload as W
+
+    if defect == "m48":
+        m &= M48
+    if e[XP] != PUSHPULL or defect not in ("kp32", "c32", "k32"):
+        return W.tcp_exchange_element(e[XP], e[XT], e[XB], e[XPUSH], e[XPULL], m)[:3]
+    T, B, Pb, Qb = e[XT], e[XB], e[XPUSH], e[XPULL]
+    kp, _, K, divisor, C = _pushpull_counts(e, defect)
+    y = m // divisor
+    r = (m - y * K) & M64
+    push = r < kp
+    in_seg = ((r if push else r - kp) * B) & M64
+    seg = Pb if push else Qb
+    G = (y * C + (0 if push else Pb) + in_seg) & M64
+    return (0 if push else 1), (y * seg + in_seg) & M64, min(B, max(seg - in_seg, 0), max(T - G, 0))
+
+
+def _exchange_position(e, m, defect=None):
+    from ctstraffic_amd import workload as W
+
+    if e[XP] != PUSHPULL or defect not in ("kp32", "k32") or m >= e[XN]:
+        return W.tcp_exchange_position(e[XP], e[XT], e[XB], e[XPUSH], e[XPULL], m)
+    B, Pb, Qb = e[XB], e[XPUSH], e[XPULL]
+    kp, _, K, divisor, _ = _pushpull_counts(e, defect)
+    y = m // divisor
+    r = (m - y * K) & M64
+    return [(y * Pb + (r * B if r < kp else Pb)) & M64, (y * Qb + (0 if r < kp else (r - kp) * B)) & M64]
+
+
+def exchange_tick(state, ids, stride, capacity, max_buffers, n_conns, defect=None):
+    """One tick of cts_tcp_exchange_send over state (exchange_state's lists, moved in place), one listed connection at
+    a time in Python integers: the planner is plan(), a buffer is workload.tcp_exchange_element's and the position
+    after the move workload.tcp_exchange_position's (the Python-integer forms, never the numpy model). defect: one of
+    DEFECTS (the planner's) or X_DEFECTS (a quantity of the closed forms cut short: kp and kq from a 32-bit P + B - 1,
+    C modulo 2^32, the division's K modulo 2^32, before + j cut to 48 bits, N - m cut to 32 bits before the min with
+    max_buffers). Returns w, prefix, taken, codes, tick (six fields), bytes_dir, slots ((receiver, length, pattern
+    offset) per written slot, None where a faulty plan leaves one out) and entries (copies, after the move)."""
+    assert defect is None or defect in DEFECTS or defect in X_DEFECTS, defect
+    w, codes = [], []
+    for c in ids:
+        want, code = 0, 4
+        if c < n_conns:
+            e = state[c]
+            formed = e[XB] != 0 and e[XP] <= DUPLEX and (e[XP] != PUSHPULL or (e[XPUSH] != 0 and e[XPULL] != 0))
+            if formed and e[XB] <= stride:
+                code = 2
+                if not e[XFIN] and e[XM] < e[XN]:
+                    left = e[XN] - e[XM]
+                    if defect == "n32":
+                        left &= M32
+                    want, code = min(left, max_buffers), 0
+        w.append(want)
+        codes.append(code)
+    prefix, taken = plan(w, capacity, defect if defect in DEFECTS else None, "tcp")
+    tick = dict.fromkeys(("bytes", "buffers", "connections_sent", "connections_finished", "connections_no_room",
+                          "connections_skipped"), 0)
+    bytes_dir, slots = [0, 0], {}
+    for i, c in enumerate(ids):
+        if codes[i] in (2, 4):
+            tick["connections_skipped"] += 1
+        elif taken[i] == 0:
+            codes[i] = 3
+            tick["connections_no_room"] += 1
+        else:
+            e = state[c]
+            for j in range(taken[i]):
+                d, pos, length = _exchange_element(e, e[XM] + j, defect)
+                slots[prefix[i] + j] = (c + d * n_conns, length, pos % 65536)
+                bytes_dir[d] += length
+            e[XM] += taken[i]
+            e[XS0], e[XS1] = _exchange_position(e, e[XM], defect)
+            tick["buffers"] += taken[i]
+            tick["connections_sent"] += 1
+            if e[XM] == e[XN]:
+                e[XFIN], codes[i] = 1, 1
+                tick["connections_finished"] += 1
+    tick["bytes"] = sum(bytes_dir)
+    total = min(tick["buffers"], capacity)
+    assert defect is not None or sorted(slots) == list(range(total))
+    return {"w": w, "prefix": prefix, "taken": taken, "codes": codes, "tick": tick, "bytes_dir": bytes_dir,
+            "slots": [slots.get(g) for g in range(total)], "entries": [list(e) for e in state]}
+
+
+def long_exchange(n_listed):
+    """Case A for the exchange tick: long_tcp's table with the patterns by turns, P and Q in 1..3B + 1, transfers of 1
+    to 3 buffers (Duplex: 2, one each way), max_buffers 2, LONG_FINISHED, two ids beyond the table, two connections
+    with B above the stride and one entry with pattern 4; the capacity is the first tick's wants less 5."""
+    key = ("exchange", n_listed)
+    if key in _LONG_CACHE:
+        return _LONG_CACHE[key]
+    settings = _long_exchange_settings()
+    ids = _long_ids(n_listed, wide=(11, 700, 13))
+    case = {"settings": settings, "finished": LONG_FINISHED, "pattern4": (13,), "ids": ids, "stride": 16,
+            "max_buffers": 2}
+    first = exchange_tick(exchange_case_state(case), ids, 16, M32, 2, LONG_TABLE)
+    case["w"], case["capacity"] = first["w"], sum(first["w"]) - 5
+    _LONG_CACHE[key] = case
+    return case
+
+
+def _long_exchange_settings():
+    """long_exchange's table, the same for every list length."""
+    from ctstraffic_amd import workload as W
+
+    if "exchange settings" in _LONG_CACHE:
+        return _LONG_CACHE["exchange settings"]
+    rng = np.random.default_rng(17)
+    settings = []
+    for c in range(LONG_TABLE):
+        B, k, pattern = int(rng.integers(1, 17)), 1 + c % 3, c % 4
+        Pb, Qb = int(rng.integers(1, 3 * B + 2)), int(rng.integers(1, 3 * B + 2))
+        if pattern in (PUSH, PULL):
+            T = int(rng.integers((k - 1) * B + 1, k * B + 1))
+        elif pattern == DUPLEX:
+            T = int(rng.integers(1, 2 * B + 1))
+        else:  # the first k buffers of the sequence, the last one cut short
+            whole = sum(W.tcp_exchange_position(PUSHPULL, 1 << 40, B, Pb, Qb, k))
+            T = whole - int(rng.integers(0, W.tcp_exchange_element(PUSHPULL, 1 << 40, B, Pb, Qb, k - 1)[2]))
+        settings.append((pattern, T, B, Pb, Qb))
+    settings[11], settings[700] = (PUSHPULL, 1000, 200, 300, 100), (DUPLEX, 5000, 129)
+    _LONG_CACHE["exchange settings"] = settings
+    return settings
+
+
+def _idle_runs_exchange(stride, lead, total, filler):
+    """Case B for the exchange tick: idle_run_tokens with four idle kinds (a finished connection, an id beyond the
+    table, B above the stride, a PushPull entry with push_bytes 0), the patterns by turns, B = stride - 3, P = 2B + 1
+    and Q = B - 1 (a cycle is the buffers B, B, 1 | B - 1). Every sender has six buffers from where it stands, so two
+    ticks of max_buffers 3 send; a PushPull one stands at buffer 2, so its first three slots are the push segment's
+    last byte, the pull segment and the next cycle's first buffer."""
+    B = stride - 3
+    Pb, Qb = 2 * B + 1, B - 1
+    tokens = idle_run_tokens(lead, total, filler, kinds=4)
+    settings, seek, finished, no_push, ids, w = [], [], [], [], [], []
+    beyond = 0
+    for what, x in tokens:
+        c = len(settings)
+        if what == "idle" and x == 1:
+            ids.append(len(tokens) + beyond)
+            beyond += 1
+            w.append(0)
+            continue
+        ids.append(c)
+        pattern = c % 4
+        if what == "send":
+            assert x == S_SLOTS, "the exchange case's senders all send %d" % S_SLOTS
+            if pattern == PUSHPULL:
+                settings.append((pattern, 2 * (Pb + Qb) - c % 5, B, Pb, Qb))
+            else:
+                settings.append((pattern, 6 * B - (2 if pattern == DUPLEX else 1) * (c % 5), B, Pb, Qb))
+            seek.append(2 if pattern == PUSHPULL else 0)
+            w.append(x)
+            continue
+        size = stride + 16 if x == 2 else B
+        settings.append((PUSHPULL if x == 3 else pattern, 2 * size - c % 5, size, Pb, Qb))
+        seek.append(0)
+        w.append(0)
+        if x == 0:
+            finished.append(c)
+        if x == 3:
+            no_push.append(c)
+    return {"settings": settings, "seek": seek, "finished": finished, "no_push": no_push, "ids": ids, "stride": stride,
+            "w": w, "capacity": total, "max_buffers": 3}
+
+
+def wide_exchange():
+    """Case C for the exchange tick: wide_tcp's table, lists and four ticks at stride 16 and B = 1, P = 5, Q = 3. The
+    huge connections (2^50 bytes, so 2^50 buffers whatever the pattern) are Push, Pull, PushPull and Duplex by turns,
+    the first of the wave of 64 a PushPull one: the seven slots of ticks 3 and 4 are its, five of the push segment
+    and two of the pull segment, then one, five and one. The small ones (2 bytes) take the patterns by turns too."""
+    base = wide_tcp()
+    settings, h = [], 0
+    for c, (T, _) in enumerate(base["settings"]):
+        if T == HUGE_TRANSFER:
+            pattern = h % 4 if c < WIDE_TCP_LISTED else (PUSHPULL + c - WIDE_TCP_LISTED) % 4
+            h += 1
+        else:
+            pattern = c % 4
+        settings.append((pattern, T, 1, 5, 3))
+    return {"settings": settings, "stride": 16, "ticks": base["ticks"], "capacity": 7}

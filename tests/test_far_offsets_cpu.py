@@ -19,7 +19,8 @@ SEAM = F.SEAM
 RING_CASES = ([("tcp", s, 0, 0) for s in F.VERIFY_STRIDES] + [("tcp", s, 3, 65535) for s in F.VERIFY_STRIDES] +
               [("ms", s, 0, 0) for s in F.VERIFY_STRIDES])
 TICK_CASES = ([("server", s, 0, "") for s in F.SERVER_STRIDES] + [("tcp", s, B, "") for s, B in F.TCP_SHAPES] +
-              [("paced", s, B, p) for s, B in F.TCP_SHAPES for p in ("cut", "unpaced")])
+              [("paced", s, B, p) for s, B in F.TCP_SHAPES for p in ("cut", "unpaced")] +
+              [("exchange", s, B, "") for s, B in F.TCP_SHAPES])
 
 
 def _rows_differ(x: dict, y: dict) -> list:
@@ -180,6 +181,12 @@ def test_tick_plans_tell_the_defects(kind, stride, B, pace):
     if kind == "paced":
         assert (5 in t1["codes"].tolist()) == (pace == "cut")
         assert (t0["tail"]["connections_pending"] > 0) == (pace == "cut")
+    if kind == "exchange":  # both directions in both ticks, and the seeked connection's turn inside the first
+        n = len(p.settings)
+        assert all(min(t["tick"]["bytes_dir"]) > 0 for t in (t0, t1)) and 3 in t0["codes"].tolist()
+        mine = [int(r) % n == 2 for r in t0["descs"]["conn_index"][: t0["written"]]]
+        assert t0["descs"]["conn_index"][: t0["written"]][mine].tolist() == [2, 2, 2 + n]
+        assert int(p.entries["buffers_sent"][2]) > 1 << 33 and {s[0] for s in p.settings} == {0, 1, 2, 3}
     good, windows = p.outcome(), p.windows()
     assert all(F.in_ranges(windows, a, b) for a, b in good["ring"].touched())
     for defect in "ab":
@@ -218,6 +225,30 @@ def test_rebased_tick_models_are_the_models(kind, stride, B, pace):
             else:
                 assert np.array_equal(x[k], y[k]), (t, k)
     assert not F.ring_differs(near.outcome()["ring"], far.outcome()["ring"], [(0, near.arena_bytes)])
+
+
+def test_one_exchange_tick_moves_more_than_4_gib():
+    """What tests/test_far_offsets_gpu.py's big tick rests on, from plan_depths.exchange_tick: direction 0 and the
+    tick's bytes need more than 32 bits, direction 1 is there, and a tick block or a sent block that keeps 32 bits of
+    a sum holds other values."""
+    import plan_depths as P
+
+    case = F.big_exchange_tick()
+    stride, B = case["stride"], case["B"]
+    assert stride == 16 << 20 and B == stride - 5 and 256 * stride == SEAM < case["capacity"] * stride
+    state = P.exchange_state(case["settings"])
+    got = P.exchange_tick(state, case["ids"], stride, case["capacity"], case["max_buffers"], len(state))
+    assert got["taken"] == [86] * 4 + [16] and got["codes"] == [0] * 5 and got["tick"]["buffers"] == 360
+    d0, d1 = got["bytes_dir"]
+    assert d0 >= SEAM and got["tick"]["bytes"] >= SEAM and d1 > 0 and d0 + d1 == got["tick"]["bytes"]
+    assert (d0, d1) == (268 * B, 92 * B)
+    narrow = [d0 % SEAM, d1 % SEAM]
+    assert narrow != got["bytes_dir"] and sum(narrow) != got["tick"]["bytes"] != got["tick"]["bytes"] % SEAM
+    # a wave that sums a direction in 32 bits: one PushPull connection alone stays below 2^32, two do not
+    assert 65 * B < SEAM <= 4 * 65 * B and all(e[P.XS0] == 65 * B and e[P.XS1] == 21 * B for e in state[:4])
+    lengths = {ln for _, ln, _ in got["slots"]}
+    assert lengths == {B} and {r // 5 for r, _, _ in got["slots"]} == {0, 1}
+    assert got["slots"][256][0] in range(10) and len(got["slots"]) == 360
 
 
 # ---- 6. accounting ---------------------------------------------------------------------------------------------------

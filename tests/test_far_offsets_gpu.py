@@ -5,7 +5,8 @@ Every test allocates one arena of 4.0 to 4.1 GiB (one of them 16 GiB + 64 MiB), 
 device; only the live spans come from the host, and only the plan's windows go back. Every comparison is exact: all n
 rows of a ring's outputs are compared on the device against the oracle's rows for the live slots and its row for a
 zero-length slot everywhere else; the counters, first-failure slots and frame sums are the oracle's; every window of
-a filled arena equals the oracle's bytes and is the sentinel around them and at the aliases mod 2^32.
+a filled arena equals the oracle's bytes and is the sentinel around them and at the aliases mod 2^32. One test holds
+a dense arena instead: an exchange tick that moves 5.6 GiB, so that its byte sums need more than 32 bits.
 """
 import numpy as np
 import pytest
@@ -15,11 +16,12 @@ import far_offsets as F
 import oracle
 from ctstraffic_amd import _lib
 from ctstraffic_amd import media_stream as M
+from ctstraffic_amd import tcp_exchange as X
 from ctstraffic_amd import tcp_senders as T
 from ctstraffic_amd import workload as W
 from ctstraffic_amd.types import (CONN_RESULT_DTYPE, CONN_STATE_DTYPE, DESC_DTYPE, DGRAM_HEADER_DTYPE,
                                   DGRAM_RECORD_DTYPE, DGRAM_STATUS_DTYPE, MS_CONN_RESULT_DTYPE, MS_SERVER_STATE_DTYPE,
-                                  RESULT_DTYPE, TCP_SENDER_DTYPE, TCP_SENDER_PACE_DTYPE)
+                                  RESULT_DTYPE, TCP_EXCHANGE_DTYPE, TCP_SENDER_DTYPE, TCP_SENDER_PACE_DTYPE)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -369,14 +371,19 @@ def test_server_ticks_across_the_seam(engine, stride):
     torch.cuda.empty_cache()
 
 
-# ---- 7. the TCP senders' ticks, plain and paced, and the receive half over their descriptors --------------------------
+# ---- 7. the TCP senders' ticks, plain and paced, the exchange tick, and the receive half over their descriptors ------
 def _tcp_ticks(engine, p: F.TickPlan):
-    stride, n_conns = p.stride, len(p.settings)
+    """kind "exchange": the receivers are 2 x the connections (direction d of connection c is receiver c + d x the
+    table's size), the entries are the 64-byte ones and the tick block has its bytes by direction."""
+    stride, n_senders = p.stride, len(p.settings)
     windows, blank = p.windows(), F.SparseRing(p.arena_bytes)
     arena = _arena(p.arena_bytes)
-    ids, paced = _ids(p.ids), p.kind == "paced"
+    ids, paced, exchange = _ids(p.ids), p.kind == "paced", p.kind == "exchange"
+    n_conns = 2 * n_senders if exchange else n_senders
     for dirty in (False, True):
-        if paced:
+        if exchange:
+            table = X.ExchangeTable(engine, p.settings, stride, p.capacity, arena_slots=1, fill=F.BACKGROUND)
+        elif paced:
             table = T.PacedSenderTable(engine, p.settings, p.pace_settings, stride, p.capacity, start_ms=1000,
                                        arena_slots=1, fill=F.BACKGROUND)
             assert np.array_equal(table.fresh_pace, p.pace)
@@ -389,7 +396,11 @@ def _tcp_ticks(engine, p: F.TickPlan):
         base, all_descs, failed = 0, [], []
         sums = dict.fromkeys(oracle.COUNTER_FIELDS, 0)
         for k, t in enumerate(p.ticks()):
-            if paced:
+            if exchange:
+                X.exchange_send(engine, arena, stride, t["first_slot"], p.capacity, ids, p.max_buffers, table.entries,
+                                n_senders, table.descs, table.scratch, codes=table.codes, tick=table.tick,
+                                sent_counters=table.sent)
+            elif paced:
                 T.senders_send_paced(engine, arena, stride, t["first_slot"], p.capacity, ids, p.max_buffers,
                                      table.senders, table.pace, n_conns, p.now[k], table.descs, table.scratch,
                                      codes=table.codes, tick=table.tick, sent_counters=table.sent)
@@ -399,10 +410,13 @@ def _tcp_ticks(engine, p: F.TickPlan):
                                sent_counters=table.sent)
             torch.cuda.synchronize()
             entries, codes, tick = table.read()
-            for f in TCP_SENDER_DTYPE.names:
+            for f in (TCP_EXCHANGE_DTYPE if exchange else TCP_SENDER_DTYPE).names:
                 assert np.array_equal(entries[f], t["entries"][f]), (k, f)
             assert np.array_equal(codes[: len(p.ids)], t["codes"]), k
-            assert {f: int(tick[f]) for f in W.TCP_SENDER_TICK_FIELDS} == t["tick"] and int(tick["reserved"]) == 0, k
+            got_tick = {f: int(tick[f]) for f in W.TCP_SENDER_TICK_FIELDS}
+            if exchange:
+                got_tick["bytes_dir"] = tick["bytes_dir"].tolist()
+            assert got_tick == t["tick"] and int(tick["reserved"]) == 0, k
             if paced:
                 assert {f: int(tick[f]) for f in W.TCP_SENDER_PACED_TAIL_FIELDS} == t["tail"], k
                 pace = table.read_pace()
@@ -450,7 +464,12 @@ def _tcp_ticks(engine, p: F.TickPlan):
         got = state.cpu().numpy().view(CONN_STATE_DTYPE)
         for f in CONN_STATE_DTYPE.names:
             assert np.array_equal(got[f], want_table[f]), (dirty, f)
-        expected_bytes = np.array([min(t, 6 * p.B) for t, _ in p.settings], dtype=np.uint64)
+        if exchange:  # what the two ticks carried to each receiver, the direction-0 receivers first
+            carried = p.ticks()[-1]["entries"]["bytes_sent"] - p.entries["bytes_sent"]
+            expected_bytes = np.concatenate([carried[:, 0], carried[:, 1]]).astype(np.uint64)
+            assert int(expected_bytes.sum()) == sum(t["tick"]["bytes"] for t in p.ticks())
+        else:
+            expected_bytes = np.array([min(t, 6 * p.B) for t, _ in p.settings], dtype=np.uint64)
         block, results = engine.new_counters(), engine.new_conn_results(n_conns)
         engine.conns_close(_ids(range(n_conns)), torch.from_numpy(expected_bytes.view(np.int64).copy()).to(DEV),
                            paths[0]["cff"], state, block, results=results)
@@ -474,6 +493,69 @@ def test_tcp_sender_ticks_across_the_seam(engine, stride, B):
 @pytest.mark.parametrize("stride,B", F.TCP_SHAPES)
 def test_paced_sender_ticks_across_the_seam(engine, stride, B, pace):
     _tcp_ticks(engine, F.TickPlan("paced", stride, B, pace=pace))
+
+
+@pytest.mark.parametrize("stride,B", F.TCP_SHAPES)
+def test_exchange_ticks_across_the_seam(engine, stride, B):
+    """Push, Pull, two PushPull (one seeked past 2^33 buffers, its turn inside the first tick), Duplex and one that
+    finds no room: tcp_exchange_descs' (first_slot + g) * stride and the senders' fill over the 48-byte tick block,
+    then cts_verify_at and the accounting over 12 receivers."""
+    _tcp_ticks(engine, F.TickPlan("exchange", stride, B))
+
+
+def test_one_exchange_tick_moves_more_than_4_gib(engine):
+    """360 buffers of 16 MiB - 5 bytes in one tick: tick.bytes, bytes_dir[0] and the sent block hold values above
+    2^32 (tcp_exchange_apply's two wave_sum64, the dir[][] words in LDS, one atomic per direction per tile), and the
+    slots run from byte 0 across byte 2^32 to 5.6 GiB. The expectation is plan_depths.exchange_tick's; the arena is
+    checked on the device by cts_verify over the tick's own descriptors, and three slots (four with the one that ends
+    at byte 2^32) are compared on the host."""
+    import plan_depths as P
+
+    case = F.big_exchange_tick()
+    stride, B, capacity = case["stride"], case["B"], case["capacity"]
+    need = capacity * stride + (1 << 30)
+    free = torch.cuda.mem_get_info(0)[0]
+    if free < need:
+        pytest.skip("the device has %d bytes free, the arena and 1 GiB are %d" % (free, need))
+    state = P.exchange_state(case["settings"])
+    n_conns = len(state)
+    want = P.exchange_tick(state, case["ids"], stride, capacity, case["max_buffers"], n_conns)
+    assert want["bytes_dir"][0] >= SEAM and want["tick"]["bytes"] >= SEAM and want["bytes_dir"][1] > 0
+    table = X.ExchangeTable(engine, case["settings"], stride, capacity, fill=F.BACKGROUND)
+    table.send(_ids(case["ids"]), case["max_buffers"])
+    torch.cuda.synchronize()
+    entries, codes, tick = table.read()
+    expected = P.exchange_records(want["entries"])
+    for f in TCP_EXCHANGE_DTYPE.names:
+        assert np.array_equal(entries[f], expected[f]), f
+    assert codes[:n_conns].tolist() == want["codes"]
+    assert {f: int(tick[f]) for f in W.TCP_SENDER_TICK_FIELDS} == want["tick"] and int(tick["reserved"]) == 0
+    assert tick["bytes_dir"].tolist() == want["bytes_dir"]
+    sent = dict.fromkeys(W.SENT_FIELDS, 0)
+    sent.update(bytes_sent=want["tick"]["bytes"], buffers_sent=capacity)
+    assert table.read_sent() == sent
+    descs = table.descs.cpu().numpy().view(DESC_DTYPE)[:capacity]
+    assert descs["byte_offset"].tolist() == [g * stride for g in range(capacity)]
+    assert list(zip(descs["conn_index"].tolist(), descs["length"].tolist(),
+                    descs["expected_pattern_offset"].tolist())) == want["slots"]
+    assert not descs["skip_head"].any()
+    # the arena: the device's verify over all 360 descriptors, then four slots and their tails on the host
+    ctr, res = engine.new_counters(), engine.new_results(capacity)
+    engine.verify(table.arena, table.descs_of(capacity), max_length_hint=stride, results=res, counters=ctr)
+    torch.cuda.synchronize()
+    got = res.cpu().numpy().view(RESULT_DTYPE)
+    assert (got["pass"] == 1).all() and not got["flags"].any()
+    total = want["tick"]["bytes"]
+    assert engine.read_counters(ctr) == {"bytes_checked": total, "bytes_ok": total, "buffers_checked": capacity,
+                                         "buffers_failed": 0, "mismatched_bytes": 0}
+    assert SEAM // stride == 256
+    for g in (0, 255, 256, capacity - 1):
+        _, length, offset = want["slots"][g]
+        slot = table.arena[g * stride:(g + 1) * stride].cpu().numpy()
+        assert np.array_equal(slot[:length], F.pattern(offset, length)), g
+        assert (slot[length:] == F.BACKGROUND).all() and stride - length == 5, g
+    del table
+    torch.cuda.empty_cache()
 
 
 # ---- 8. the accounting passes over a ring of 4 GiB: no arena -------------------------------------------------------

@@ -14,6 +14,10 @@ n + 1 words, prefix[0 .. n], are compared with the model's prefix as well. Every
   path 3   test_wide_sums_tcp (plain and paced; ticks 1, 3 and 4)
   path 4   test_idle_runs_ms, test_idle_runs_ms_one_workgroup_per_cu
   path 5   test_descs_in_two_passes; the search over a long prefix[] also in test_idle_runs_tcp and the long lists
+
+The exchange tick (tcp_exchange_sums / _scan / _apply, tcp_exchange_descs) takes paths 1, 2, 3 and the long search in
+test_long_list_exchange, test_wide_sums_exchange and test_idle_runs_exchange, compared with the numpy model and with
+plan_depths.exchange_tick (tests/test_tcp_exchange_gpu.py has its second grid-stride pass).
 """
 import os
 
@@ -274,3 +278,91 @@ def test_wide_sums_ms(engine):
         _same_prefix(table, got["prefix"], got["w"], "tick %d" % t)
         assert view.codes.tolist() == [0] * 4 + [3] * (n - 4) and view.tick["datagrams"] == 8
         assert got["prefix"][-1] > 1 << 32
+
+
+# ---- the exchange tick (tcp_exchange_sums / _scan / _apply, tcp_exchange_descs) on the same three cases --------------
+def _exchange_pair(engine, case, capacity, n_listed):
+    from test_tcp_exchange_gpu import Pair as ExchangePair
+
+    entries = P.exchange_records(P.exchange_case_state(case))
+    return ExchangePair(engine, case["settings"], case["stride"], capacity, max_listed=n_listed, entries=entries)
+
+
+def _same_exchange_plan(p, v, got, where):
+    """The model's tick v and the scratch's prefix[] against exchange_tick's result: the plan, the codes, the tick,
+    the entries and, per written slot, receiver, length and pattern offset."""
+    assert [int(x) for x in v.prefix] == got["prefix"] and [int(x) for x in v.taken] == got["taken"], where
+    _same_prefix(p.table, v.prefix, got["w"], where)
+    assert v.codes.tolist() == got["codes"] and v.tick == dict(got["tick"], bytes_dir=got["bytes_dir"]), where
+    total = got["tick"]["buffers"]
+    d = v.descs[:total]
+    assert list(zip(d["conn_index"].tolist(), d["length"].tolist(),
+                    d["expected_pattern_offset"].tolist())) == got["slots"], where
+    assert np.array_equal(p.entries, P.exchange_records(got["entries"])), where
+
+
+@pytest.mark.parametrize("n_listed", P.LONG_LISTED)
+def test_long_list_exchange(engine, n_listed):
+    """long_tcp's table with the patterns by turns, P and Q in 1..3B + 1, finished connections, two ids beyond the
+    table, two with B above the stride, one entry with pattern 4, and a capacity 5 below the first tick's wants: a
+    non-zero carry into the scan's second pass, a sender behind it, the tail cut; ticked to the end."""
+    case = P.long_exchange(n_listed)
+    f = _tcp_facts(engine, case["w"], case["capacity"])
+    assert P.long_reaches(case, n_listed, f) == [] and f["search_steps_max"] >= 16, f
+    p = _exchange_pair(engine, case, case["capacity"], n_listed)
+    state, seen = P.exchange_case_state(case), set()
+    for t in range(6):
+        v = p.tick(case["ids"], 2, where="tick %d" % t)
+        got = P.exchange_tick(state, case["ids"], 16, case["capacity"], 2, P.LONG_TABLE)
+        assert got["w"] == case["w"] or t
+        _same_exchange_plan(p, v, got, "tick %d" % t)
+        assert t or (3 in v.codes[-64:] and v.tick["buffers"] == case["capacity"] and min(v.tick["bytes_dir"]) > 0)
+        assert t or n_listed == 65_536 or int(v.prefix[65_536]) > 0
+        seen |= set(v.codes.tolist())
+        if v.tick["buffers"] == 0:
+            break
+    assert {0, 1, 2, 3, 4} <= seen and 2 <= t <= 4 and set(v.codes.tolist()) == {2, 4}
+
+
+def test_idle_runs_exchange(engine):
+    """The idle runs of 511, 512, 513 and 1500 through tcp_exchange_descs: finished connections, ids beyond the table,
+    B above the stride and PushPull entries with push_bytes 0 between two slots' owners; every PushPull sender's three
+    slots cross a turn. Two ticks."""
+    case = P.idle_runs("exchange", 64)
+    f = _tcp_facts(engine, case["w"], case["capacity"])
+    assert P.idle_descs_reaches(f) == [], f
+    n = len(case["ids"])
+    p = _exchange_pair(engine, case, case["capacity"], n)
+    state = P.exchange_case_state(case)
+    for t in range(2):
+        v = p.tick(case["ids"], 3, where="tick %d" % t)
+        got = P.exchange_tick(state, case["ids"], 64, case["capacity"], 3, len(state))
+        assert got["w"] == case["w"]
+        _same_exchange_plan(p, v, got, "tick %d" % t)
+        assert v.tick["buffers"] == case["capacity"] and set(v.codes.tolist()) == {t, 2, 4}
+    assert (p.entries["finished"][[c for c, x in zip(case["ids"], case["w"]) if x]] == 1).all()
+
+
+def test_wide_sums_exchange(engine):
+    """wide_tcp's four ticks with 2^50-byte Push, Pull, PushPull and Duplex connections at B = 1: wants of 2^31 and
+    0xFFFFFFFF from N - m beside capacities of 7 and 0."""
+    case = P.wide_exchange()
+    n_max = max(len(t["ids"]) for t in case["ticks"])
+    state = P.exchange_case_state(case)
+    p = _exchange_pair(engine, case, 7, n_max)
+    n_conns = len(state)
+    for k, t in enumerate(case["ticks"]):
+        got = P.exchange_tick(state, t["ids"], 16, t["capacity"], t["max_buffers"], n_conns)
+        f = _tcp_facts(engine, got["w"], t["capacity"])
+        assert P.wide_tcp_reaches(k, f) == [], (k, {x: y for x, y in f.items() if x != "prefixes"})
+        v = p.tick(t["ids"], t["max_buffers"], capacity=t["capacity"], where="tick %d" % k)
+        _same_exchange_plan(p, v, got, "tick %d" % k)
+        if k == 0:
+            assert v.taken[:3].tolist() == [2, 5, 0] and set(v.codes[2:].tolist()) == {3}
+            assert [int(x) for x in v.prefix[:4]] == [0, 2, 2 + (1 << 31), 2 + (1 << 32)]
+        elif k == 1:
+            assert v.tick["buffers"] == 0 and set(v.codes.tolist()) == {2, 3}
+        else:  # seven buffers of one PushPull connection: both of its receivers
+            assert v.taken[0] == 7 and int(v.prefix[1]) == 0xFFFFFFFF
+            assert set(v.descs["conn_index"][:7].tolist()) == {t["ids"][0], t["ids"][0] + n_conns}
+            assert min(v.tick["bytes_dir"]) >= 2

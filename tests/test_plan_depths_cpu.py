@@ -8,6 +8,8 @@
 4. Sensitivity: every defect of plan_depths is told from the defect-free planner by the case built for it, and the
    defect-free planner equals the numpy model on every case.
 5. The numpy models at the long lists' size equal one-connection-at-a-time loops in Python integers.
+6. The exchange tick's three cases reach the same facts, the planner's defects each change the outcome of one of them,
+   and workload.tcp_exchange_view equals plan_depths.exchange_tick on all of them.
 """
 import numpy as np
 import pytest
@@ -346,3 +348,121 @@ def test_ms_model_on_a_long_list_is_the_loop():
         assert view.entries["current_frame"].tolist() == [e[3] for e in state]
         assert view.entries["finished"].tolist() == [e[5] for e in state]
     assert {0, 1, 2, 3, 4} <= seen
+
+
+# ---- 6. the exchange tick on the same cases --------------------------------------------------------------------------
+def _exchange_view_ticks(case, ticks, capacity_max):
+    """The numpy model and exchange_tick side by side over a case's ticks (ids, max_buffers, capacity): yields
+    (k, view, exchange_tick's result)."""
+    state = P.exchange_case_state(case)
+    entries = P.exchange_records(state)
+    arena = np.zeros(max(1, capacity_max) * case["stride"], dtype=np.uint8)
+    for k, (ids, max_buffers, capacity) in enumerate(ticks):
+        v = W.tcp_exchange_view(entries, case["stride"], arena, 0, capacity, ids, max_buffers)
+        got = P.exchange_tick(state, ids, case["stride"], capacity, max_buffers, len(state))
+        entries = v.entries
+        assert [int(x) for x in v.prefix] == got["prefix"] and [int(x) for x in v.taken] == got["taken"], k
+        assert v.codes.tolist() == got["codes"] and v.tick == dict(got["tick"], bytes_dir=got["bytes_dir"]), k
+        d = v.descs[: got["tick"]["buffers"]]
+        assert list(zip(d["conn_index"].tolist(), d["length"].tolist(),
+                        d["expected_pattern_offset"].tolist())) == got["slots"], k
+        assert np.array_equal(entries, P.exchange_records(got["entries"])), k
+        yield k, v, got
+
+
+@pytest.mark.parametrize("n_listed", P.LONG_LISTED)
+def test_long_exchange_reaches_the_second_pass(n_listed):
+    case = P.long_exchange(n_listed)
+    f = P.facts(case["w"], case["capacity"], "tcp")
+    assert P.long_reaches(case, n_listed, f) == [], f
+    assert (1 in P.reaches(f)) == (n_listed > 65_536)
+    ids = case["ids"]
+    assert ids.count(P.LONG_TABLE) == ids.count(0xFFFFFFFF) == 1 and len(set(ids)) == n_listed
+    assert {11, 700, 13} <= set(ids) and case["pattern4"] == (13,)
+    state = P.exchange_case_state(case)
+    assert {e[P.XP] for e in state} == {0, 1, 2, 3, 4} and sum(e[P.XFIN] for e in state) == len(P.LONG_FINISHED)
+    assert [c for c, e in enumerate(state) if e[P.XB] > 16] == [11, 700]
+    table = [e for c, e in enumerate(state) if c not in (11, 700)]
+    assert {e[P.XN] for e in table} == {1, 2, 3}
+    assert all(1 <= e[P.XPUSH] <= 3 * e[P.XB] + 1 and 1 <= e[P.XPULL] <= 3 * e[P.XB] + 1 for e in table)
+    for defect in ("prefix32", "limb_carry"):  # a list of wants of 1 and 2 tells neither apart: the wide case does
+        assert P.plan(case["w"], case["capacity"], defect) == P.plan(case["w"], case["capacity"])
+
+
+def test_long_exchange_model_is_the_loop_to_the_end():
+    case = P.long_exchange(65_829)
+    ticks = [(case["ids"], 2, case["capacity"])] * 4
+    seen = set()
+    for k, v, got in _exchange_view_ticks(case, ticks, case["capacity"]):
+        seen |= set(got["codes"])
+        assert k or (got["codes"][-64:].count(3) >= 1 and got["tick"]["buffers"] == case["capacity"])
+    assert {0, 1, 2, 3, 4} <= seen and got["tick"]["buffers"] == 0 and set(got["codes"]) == {2, 4}
+
+
+@pytest.mark.parametrize("cus", CUS)
+def test_idle_runs_exchange_reach_the_long_search(cus):
+    case = P.idle_runs("exchange", 64)
+    f = P.facts(case["w"], case["capacity"], "tcp", cus)
+    assert P.idle_descs_reaches(f) == [], f
+    if cus != CUS[0]:
+        return
+    state = P.exchange_case_state(case)
+    idle = [state[c] for c, x in zip(case["ids"], case["w"]) if x == 0 and c < len(state)]
+    assert sum(e[P.XFIN] for e in idle) > 500 and sum(e[P.XB] > 64 for e in idle) > 500
+    assert sum(e[P.XPUSH] == 0 and e[P.XP] == P.PUSHPULL for e in idle) > 500
+    assert sum(1 for c in case["ids"] if c >= len(state)) > 500
+    ticks = [(case["ids"], 3, case["capacity"])] * 2
+    for k, v, got in _exchange_view_ticks(case, ticks, case["capacity"]):
+        assert got["w"] == case["w"] and got["tick"]["buffers"] == case["capacity"]
+        assert set(got["codes"]) == {k, 2, 4}
+        # every PushPull sender's three slots are both directions'
+        n = len(state)
+        for i, c in enumerate(case["ids"]):
+            if case["w"][i] and state[c][P.XP] == P.PUSHPULL:
+                mine = got["slots"][got["prefix"][i]: got["prefix"][i] + 3]
+                assert {r for r, _, _ in mine} == {c, c + n}, (k, c, mine)
+
+
+def test_wide_exchange_reaches_64_bits():
+    case = P.wide_exchange()
+    assert [t["capacity"] for t in case["ticks"]] == [7, 0, 7, 7]
+    assert [t["max_buffers"] for t in case["ticks"]] == [0x80000000] + [0xFFFFFFFF] * 3
+    state = P.exchange_case_state(case)
+    huge = [e for e in state if e[P.XT] == P.HUGE_TRANSFER]
+    assert {e[P.XP] for e in huge} == {0, 1, 2, 3} and all(e[P.XN] == 1 << 50 and e[P.XB] == 1 for e in huge)
+    assert state[P.WIDE_TCP_LISTED][P.XP] == P.PUSHPULL and state[P.WIDE_TCP_LISTED][3:5] == [5, 3]
+    ticks = [(t["ids"], t["max_buffers"], t["capacity"]) for t in case["ticks"]]
+    for k, v, got in _exchange_view_ticks(case, ticks, 7):
+        f = P.facts(got["w"], ticks[k][2], "tcp")
+        assert P.wide_tcp_reaches(k, f) == [], (k, f)
+        if k >= 2:
+            first = ticks[k][0][0]
+            assert got["taken"][0] == 7 and {r for r, _, _ in got["slots"]} == {first, first + len(state)}
+    assert [r // len(state) for r, _, _ in got["slots"]] == [1, 0, 0, 0, 0, 0, 1]
+
+
+def test_every_planner_defect_shows_in_an_exchange_case():
+    """prefix32 and limb_carry on the wide case, no_carry on the long list, descs_one_pass on the long list at four
+    compute units and one workgroup per CU: each changes what a GPU test compares."""
+    told = {}
+    wide = P.wide_exchange()
+    for defect, k in (("prefix32", 0), ("limb_carry", 3)):
+        outcomes = []
+        for d in (None, defect):
+            state = P.exchange_case_state(wide)
+            for t in wide["ticks"][:k + 1]:
+                got = P.exchange_tick(state, t["ids"], 16, t["capacity"], t["max_buffers"], len(state), d)
+            outcomes.append((got["prefix"], got["taken"], got["codes"], got["slots"], got["entries"]))
+        told[defect] = outcomes[0] != outcomes[1]
+    long_case = P.long_exchange(65_537)
+    outcomes = []
+    for d in (None, "no_carry"):
+        got = P.exchange_tick(P.exchange_case_state(long_case), long_case["ids"], 16, long_case["capacity"], 2,
+                              P.LONG_TABLE, d)
+        outcomes.append((got["prefix"], got["taken"], got["codes"], got["entries"]))
+    told["no_carry"] = outcomes[0] != outcomes[1]
+    w, capacity = long_case["w"], long_case["capacity"]
+    good = P.slot_owners(w, capacity, "tcp", 4, 1)
+    assert None not in good and P.facts(w, capacity, "tcp", 4, blocks_per_cu=1)["descs_passes_max"] > 1
+    told["descs_one_pass"] = P.slot_owners(w, capacity, "tcp", 4, 1, "descs_one_pass") != good
+    assert all(told.values()) and set(told) == set(P.DEFECTS) - {"staged_only"}, told
