@@ -2,7 +2,7 @@
 #   make            -> ctstraffic_amd/libcts_engine.so (the product: one kernel per path) + oracle/libcts_oracle.so +
 #                      the C++ device samples (ctstraffic_amd/build/device_verify, device_connections,
 #                      device_ms_connections, device_ms_servers, device_tcp_senders, device_tcp_paced_senders,
-#                      device_tcp_exchange) + what bench.py
+#                      device_tcp_exchange, device_tcp_paced_exchange) + what bench.py
 #                      and the tests run
 #                      (tools/libcts_bench_multi.so, tools/pattern_cpu_probe)
 #   make probes     -> the measurement probes of tools/ (ceilings, timelines, ablations; built before an A/B call)
@@ -28,13 +28,14 @@ DEVICE_MS_SERVERS := ctstraffic_amd/build/device_ms_servers
 DEVICE_TCP_SENDERS := ctstraffic_amd/build/device_tcp_senders
 DEVICE_TCP_PACED_SENDERS := ctstraffic_amd/build/device_tcp_paced_senders
 DEVICE_TCP_EXCHANGE := ctstraffic_amd/build/device_tcp_exchange
+DEVICE_TCP_PACED_EXCHANGE := ctstraffic_amd/build/device_tcp_paced_exchange
 PROBES := tools/hbm_read_ceiling tools/verify_ablation tools/mailbox_probe tools/rw_mix_probe tools/write_shape_probe \
           tools/fill_bisect tools/fill_abi_probe tools/mailbox_bisect tools/ring_fill_probe tools/verify_timeline \
           tools/verify_timeline_kp tools/sync_probe tools/deferred_ab tools/slab_verify_probe tools/write_ceiling_rot tools/ring_order_probe \
           tools/first_read_probe
 BENCH_MULTI := tools/libcts_bench_multi.so
 
-all: $(ENGINE_SO) oracle $(DEVICE_VERIFY) $(DEVICE_CONNECTIONS) $(DEVICE_MS_CONNECTIONS) $(DEVICE_MS_SERVERS) $(DEVICE_TCP_SENDERS) $(DEVICE_TCP_PACED_SENDERS) $(DEVICE_TCP_EXCHANGE) $(BENCH_MULTI) tools/pattern_cpu_probe
+all: $(ENGINE_SO) oracle $(DEVICE_VERIFY) $(DEVICE_CONNECTIONS) $(DEVICE_MS_CONNECTIONS) $(DEVICE_MS_SERVERS) $(DEVICE_TCP_SENDERS) $(DEVICE_TCP_PACED_SENDERS) $(DEVICE_TCP_EXCHANGE) $(DEVICE_TCP_PACED_EXCHANGE) $(BENCH_MULTI) tools/pattern_cpu_probe
 
 probes: $(PROBES)
 
@@ -138,6 +139,11 @@ $(DEVICE_TCP_PACED_SENDERS): tests/cpp/device_tcp_paced_senders.cpp $(ENGINE_SO)
 
 # C++ PushPull exchange sample against the C ABI (run on the GPU box by tests/test_cpp_tcp_exchange.py)
 $(DEVICE_TCP_EXCHANGE): tests/cpp/device_tcp_exchange.cpp $(ENGINE_SO) $(wildcard include/*.h)
+	@mkdir -p ctstraffic_amd/build
+	$(HIPCC) -O2 -std=c++17 -Iinclude $< -o $@ -Lctstraffic_amd -lcts_engine -Wl,-rpath,'$$ORIGIN/..'
+
+# C++ paced PushPull exchange sample against the C ABI (run on the GPU box by tests/test_cpp_tcp_paced_exchange.py)
+$(DEVICE_TCP_PACED_EXCHANGE): tests/cpp/device_tcp_paced_exchange.cpp $(ENGINE_SO) $(wildcard include/*.h)
 	@mkdir -p ctstraffic_amd/build
 	$(HIPCC) -O2 -std=c++17 -Iinclude $< -o $@ -Lctstraffic_amd -lcts_engine -Wl,-rpath,'$$ORIGIN/..'
 

@@ -257,6 +257,9 @@ def _declare(L: ctypes.CDLL) -> None:
         "cts_tcp_exchange_scratch_bytes": ([u32], ctypes.c_size_t),
         "cts_tcp_exchange_send": ([P, P, u64, u32, u64, u32, P, u32, u32, P, u32, P, P, P, P, P, ctypes.c_size_t, P],
                                   i32),
+        "cts_tcp_exchange_paced_scratch_bytes": ([u32], ctypes.c_size_t),
+        "cts_tcp_exchange_send_paced": ([P, P, u64, u32, u64, u32, P, u32, u32, P, P, u32, ctypes.c_int64, P, P, P, P,
+                                         P, ctypes.c_size_t, P], i32),
         "cts_counters_read_sent": ([P, P, ctypes.POINTER(CtsCountersSent), P], i32),
         "cts_counters_read_multi_sent": ([ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), u32,
                                           ctypes.POINTER(CtsCountersSent)], i32),

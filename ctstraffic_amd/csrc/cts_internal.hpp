@@ -318,8 +318,31 @@ hipError_t launch_tcp_exchange_descs(uint32_t stride, uint64_t first_slot, uint3
                                      const TcpExchangeScratch& scratch, const cts_tcp_exchange_tick* tick,
                                      cts_buf_desc* descs, hipStream_t stream, const LaunchGeometry& geo);
 
-// What the arguments of a TCP tick must satisfy (cts_tcp_senders_send, _send_paced, cts_tcp_exchange_send) once
-// n != 0; dev_entries = the connections' table, need = the scratch size of that tick.
+// The paced exchange tick (cts_tcp_exchange_send_paced). Its scratch is the exchange tick's with the 64-byte tick
+// block at the end: the descriptor pass reads the block's first 48 bytes as the exchange tick it expects, the fill its
+// first 32.
+struct TcpExchangePacedScratch {
+    TcpExchangeScratch exchange;
+    cts_tcp_exchange_paced_tick* tick;  // 1
+    TcpExchangePacedScratch(void* base, uint32_t n)
+        : exchange(base, n), tick(reinterpret_cast<cts_tcp_exchange_paced_tick*>(exchange.tick))
+    {
+    }
+    static size_t bytes(uint32_t n)
+    {
+        return TcpExchangeScratch::bytes(n) - sizeof(cts_tcp_exchange_tick) + sizeof(cts_tcp_exchange_paced_tick);
+    }
+};
+// The paced planning (three launches: tcp_exchange_paced_sums, _scan, _apply): what launch_tcp_exchange_plan writes,
+// with the wanted slots cut by the 2 x n_conns pace entries at now_ms, the pace entries moved, and the tick's tail.
+hipError_t launch_tcp_exchange_paced_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
+                                          cts_tcp_exchange_state* entries, cts_tcp_sender_pace* pace,
+                                          uint32_t n_conns, int64_t now_ms, uint32_t stride, uint32_t capacity,
+                                          uint32_t* codes, cts_tcp_exchange_paced_tick* tick, uint64_t* sent_counters,
+                                          const TcpExchangePacedScratch& scratch, hipStream_t stream);
+
+// What the arguments of a TCP tick must satisfy (cts_tcp_senders_send, _send_paced, cts_tcp_exchange_send,
+// _send_paced) once n != 0; dev_entries = the connections' table, need = the scratch size of that tick.
 inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1u)) != 0; }
 inline bool tick_args_ok(const void* dev_arena, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
                          uint32_t capacity, const uint32_t* dev_conn_ids, uint32_t max_buffers,

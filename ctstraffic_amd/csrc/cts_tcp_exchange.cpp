@@ -1,6 +1,6 @@
 // cts_tcp_exchange.cpp — Push, Pull, PushPull and Duplex connections on the device-resident path
 // (cts_tcp_exchange.h): the host-side entry helpers (cts_tcp_exchange_init, _seek, _where, _direction_bytes), the
-// scratch size and the tick (cts_tcp_exchange_send).
+// scratch sizes, the tick (cts_tcp_exchange_send) and the paced tick (cts_tcp_exchange_send_paced).
 //
 // A translation unit of its own, like cts_tcp_senders.cpp: nothing else in the library references these entry points.
 // The helpers are the closed forms of cts_tcp_exchange_math.hpp, the ones the kernels run: no loop over buffers, so a
@@ -16,6 +16,9 @@ static_assert(sizeof(cts_tcp_exchange_state) == 64 && alignof(cts_tcp_exchange_s
 static_assert(sizeof(cts_tcp_exchange_tick) == 48 && alignof(cts_tcp_exchange_tick) == 8 &&
                   offsetof(cts_tcp_exchange_tick, bytes_dir) == 32,
               "cts_tcp_exchange_tick: a plain tick and 16 bytes");
+static_assert(sizeof(cts_tcp_exchange_paced_tick) == 64 && alignof(cts_tcp_exchange_paced_tick) == 8 &&
+                  offsetof(cts_tcp_exchange_paced_tick, next_due_ms) == 48,
+              "cts_tcp_exchange_paced_tick: an exchange tick and 16 bytes");
 
 namespace {
 
@@ -141,6 +144,45 @@ int cts_tcp_exchange_send(cts_engine* e, void* dev_arena, uint64_t arena_bytes, 
     // the fill is the senders': it reads the block's first 32 bytes
     return cts::launch_tcp_sender_fill(static_cast<uint8_t*>(dev_arena), arena_bytes, stride, capacity, dev_descs,
                                        &tick->tick, s, geo) == hipSuccess
+               ? CTS_OK
+               : CTS_E_HIP;
+}
+
+size_t cts_tcp_exchange_paced_scratch_bytes(uint32_t n) { return cts::TcpExchangePacedScratch::bytes(n); }
+
+int cts_tcp_exchange_send_paced(cts_engine* e, void* dev_arena, uint64_t arena_bytes, uint32_t stride,
+                                uint64_t first_slot, uint32_t capacity, const uint32_t* dev_conn_ids, uint32_t n,
+                                uint32_t max_buffers, cts_tcp_exchange_state* dev_entries,
+                                cts_tcp_sender_pace* dev_pace, uint32_t n_conns, int64_t now_ms,
+                                cts_buf_desc* dev_descs, uint32_t* dev_codes, cts_tcp_exchange_paced_tick* dev_tick,
+                                void* dev_sent_counters, void* dev_scratch, size_t scratch_bytes, void* stream)
+{
+    if (e == nullptr) return CTS_E_INVALID;
+    if (n == 0) return CTS_OK;
+    if (!cts::tick_args_ok(dev_arena, arena_bytes, stride, first_slot, capacity, dev_conn_ids, max_buffers,
+                           dev_entries, n_conns, dev_descs, dev_codes, dev_tick, dev_sent_counters, dev_scratch,
+                           scratch_bytes, cts::TcpExchangePacedScratch::bytes(n)))
+        return CTS_E_INVALID;
+    if (n_conns > (1u << 31)) return CTS_E_INVALID;  // receiver and pace entry c + n_conns
+    if (now_ms < 0) return CTS_E_INVALID;
+    if ((n_conns != 0 && dev_pace == nullptr) || cts::misaligned(dev_pace, 8)) return CTS_E_INVALID;
+    int device = 0;
+    const cts::LaunchGeometry& geo = cts::engine_geometry(e, &device);
+    DeviceGuard g(device);
+    if (!g.ok) return CTS_E_HIP;
+    const cts::TcpExchangePacedScratch scratch(dev_scratch, n);
+    cts_tcp_exchange_paced_tick* const tick = dev_tick != nullptr ? dev_tick : scratch.tick;
+    hipStream_t const s = static_cast<hipStream_t>(stream);
+    hipError_t rc = cts::launch_tcp_exchange_paced_plan(dev_conn_ids, n, max_buffers, dev_entries, dev_pace, n_conns,
+                                                        now_ms, stride, capacity, dev_codes, tick,
+                                                        static_cast<uint64_t*>(dev_sent_counters), scratch, s);
+    if (rc != hipSuccess) return CTS_E_HIP;
+    // the descriptor pass and the fill are the plain tick's: they read the block's first 48 and 32 bytes
+    rc = cts::launch_tcp_exchange_descs(stride, first_slot, capacity, dev_conn_ids, n, dev_entries, n_conns,
+                                        scratch.exchange, &tick->tick, dev_descs, s, geo);
+    if (rc != hipSuccess) return CTS_E_HIP;
+    return cts::launch_tcp_sender_fill(static_cast<uint8_t*>(dev_arena), arena_bytes, stride, capacity, dev_descs,
+                                       &tick->tick.tick, s, geo) == hipSuccess
                ? CTS_OK
                : CTS_E_HIP;
 }

@@ -105,6 +105,71 @@ CTS_XCH_FN void exchange_element(const ExchangeShape& s, uint64_t m, uint32_t& d
     }
 }
 
+// The sequence one element at a time, for a walk that has to look at every buffer (the paced tick): seeded by one
+// closed-form evaluation at m, then moved by additions only. For PushPull this is the reference's own machine
+// (m_sending, m_intraSegmentTransfer, the remaining transfer); the lengths are exchange_element's.
+struct ExchangeCursor {
+    uint64_t left;   // PushPull: bytes left of T; otherwise bytes left of direction d's stream
+    uint64_t other;  // Duplex: bytes left of the other direction's stream
+    uint32_t d;      // the direction of the next buffer
+    uint32_t intra;  // PushPull: m_intraSegmentTransfer
+
+    CTS_XCH_FN void seed(const ExchangeShape& s, uint64_t m)
+    {
+        const uint64_t B = s.B;
+        other = 0u;
+        intra = 0u;
+        switch (s.pattern) {
+            case CTS_TCP_EXCHANGE_PUSH:
+            case CTS_TCP_EXCHANGE_PULL:
+                d = s.pattern == CTS_TCP_EXCHANGE_PULL ? 1u : 0u;
+                left = exchange_sub(s.T, m * B);
+                return;
+            case CTS_TCP_EXCHANGE_DUPLEX:
+                // after an odd m direction 0 is one buffer ahead of direction 1
+                d = (uint32_t)(m & 1u);
+                left = exchange_sub(exchange_half(s.T), (m >> 1) * B);
+                other = d == 0u ? left : exchange_sub(left, B);
+                return;
+            default: {
+                const uint64_t kp = ((uint64_t)s.P + B - 1u) / B, kq = ((uint64_t)s.Q + B - 1u) / B, K = kp + kq;
+                const uint64_t y = m / K, r = m - y * K, C = (uint64_t)s.P + s.Q;
+                const bool push = r < kp;
+                const uint64_t in_seg = (push ? r : r - kp) * B;  // < the segment's size: r counts whole buffers
+                d = push ? 0u : 1u;
+                intra = (uint32_t)in_seg;
+                left = exchange_sub(s.T, y * C + (push ? 0u : s.P) + in_seg);
+                return;
+            }
+        }
+    }
+    // The length of the next buffer: min(B, bytes left[, segment - intra]).
+    CTS_XCH_FN uint32_t len(const ExchangeShape& s) const
+    {
+        uint64_t n = exchange_min(s.B, left);
+        if (s.pattern == CTS_TCP_EXCHANGE_PUSHPULL) n = exchange_min(n, (d == 0u ? s.P : s.Q) - intra);
+        return (uint32_t)n;
+    }
+    // Past a buffer of n = len(s) bytes; true when the direction has changed.
+    CTS_XCH_FN bool advance(const ExchangeShape& s, uint32_t n)
+    {
+        left -= n;
+        if (s.pattern == CTS_TCP_EXCHANGE_DUPLEX) {
+            const uint64_t mine = left;
+            left = other;
+            other = mine;
+            d ^= 1u;
+            return true;
+        }
+        if (s.pattern != CTS_TCP_EXCHANGE_PUSHPULL) return false;
+        intra += n;
+        if (intra < (d == 0u ? s.P : s.Q)) return false;
+        d ^= 1u;
+        intra = 0u;
+        return true;
+    }
+};
+
 // The bytes each direction has sent once the first m <= N buffers are out.
 CTS_XCH_FN void exchange_position(const ExchangeShape& s, uint64_t m, uint64_t (&sent)[2])
 {

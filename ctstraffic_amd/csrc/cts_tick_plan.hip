@@ -1,9 +1,9 @@
 // cts_tick_plan.hip — the planning of a device-resident sender's tick for gfx950: which ring slots every listed
-// connection takes, with no pattern byte written. Four ticks plan the same way (cts_media_stream_servers_send,
-// cts_tcp_senders_send, cts_tcp_senders_send_paced, cts_tcp_exchange_send): listed connection i wants w_i slots (0 when it sends nothing
-// whatever the room); p_i, the exclusive 64-bit prefix of the wants in listed order, is its first slot, and the room
-// left at p_i decides what it takes. Three plain launches in tiles of kPlanTile listed connections (no workgroup ever
-// waits for another):
+// connection takes, with no pattern byte written. Five ticks plan the same way (cts_media_stream_servers_send,
+// cts_tcp_senders_send, cts_tcp_senders_send_paced, cts_tcp_exchange_send, cts_tcp_exchange_send_paced): listed
+// connection i wants w_i slots (0 when it sends nothing whatever the room); p_i, the exclusive 64-bit prefix of the
+// wants in listed order, is its first slot, and the room left at p_i decides what it takes. Three plain launches in
+// tiles of kPlanTile listed connections (no workgroup ever waits for another):
 //   *_sums    each tile's sum of wants                              -> sums[tile]
 //   *_scan    one workgroup: exclusive scan of the tile sums in place in passes of kBlock tiles, prefix[n] = the grand
 //             total, the tick block initialised
@@ -15,6 +15,8 @@
 //                                       (ctsIOPattern.cpp:593-674) lets out at now_ms, from a pace entry per connection
 //   tcp_exchange_sums / _scan / _apply  the exchange tick (cts_tcp_exchange_send): Push, Pull, PushPull and Duplex
 //                                       connections, the wants counted in buffers of a fixed sequence
+//   tcp_exchange_paced_sums / _scan / _apply  the paced exchange tick (cts_tcp_exchange_send_paced): those wants cut
+//                                       by the pace entries of the two sides, one walk over directions and quanta
 // Each step of the scheme is written once here (the tile scan, the tile-sum tail, the scan's passes, the TCP limit, the
 // TCP entry move, the apply tail). What writes the ring from prefix[] is in cts_fill.hip, beside the loops it shares
 // with the other fills.
@@ -119,6 +121,32 @@ __device__ __forceinline__ void apply_flush(const uint32_t (&words)[WORDS], uint
 #pragma unroll
         for (int w = 0; w < kBlock / 64; ++w) s += wsum[w];
         if (s) atomicAdd((unsigned long long*)tick_bytes, (unsigned long long)s);
+    }
+}
+
+// Beside apply_flush, for the ticks whose block has more than words and bytes: thread `at` of the workgroup takes the
+// minimum of the waves' due[] to *tick_due (one 64-bit atomicMin per workgroup, none where nothing is pending), and
+// threads at, at + 1 add the waves' dir[][0 .. 1] to tick_dir. Both arrays are written before apply_flush's barrier.
+constexpr int64_t kNoDue = INT64_MAX;
+
+__device__ __forceinline__ void apply_flush_due(const int64_t* due, int64_t* tick_due, uint32_t at)
+{
+    if (threadIdx.x == at) {
+        int64_t m = kNoDue;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) m = due[w] < m ? due[w] : m;
+        if (m != kNoDue) atomicMin((long long*)tick_due, (long long)m);
+    }
+}
+
+__device__ __forceinline__ void apply_flush_dir(const uint64_t (*dir)[2], uint64_t* tick_dir, uint32_t at)
+{
+    if (threadIdx.x >= at && threadIdx.x < at + 2u) {
+        const uint32_t d = threadIdx.x - at;
+        uint64_t s = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) s += dir[w][d];
+        if (s) atomicAdd((unsigned long long*)&tick_dir[d], (unsigned long long)s);
     }
 }
 
@@ -388,8 +416,6 @@ hipError_t launch_tcp_sender_plan(const uint32_t* conn_ids, uint32_t n, uint32_t
 
 namespace {
 
-constexpr int64_t kNoDue = INT64_MAX;
-
 // The members of a pace entry that a tick reads, in registers; save() stores the five that a tick moves.
 struct PaceRegs {
     int64_t per, cur, start, due;
@@ -625,13 +651,7 @@ __global__ void __launch_bounds__(kBlock)
         words, bytes, red, wsum, ctr, sent_block,
         [&](uint32_t k) { return k < 5u ? &tick->tick.buffers + k : &tick->connections_waiting + (k - 5u); },
         &tick->tick.bytes);
-    if (threadIdx.x == 8u) {
-        // one 64-bit minimum per workgroup, and none where nothing is pending
-        int64_t m = kNoDue;
-#pragma unroll
-        for (int w = 0; w < kBlock / 64; ++w) m = due[w] < m ? due[w] : m;
-        if (m != kNoDue) atomicMin((long long*)&tick->next_due_ms, (long long)m);
-    }
+    apply_flush_due(due, &tick->next_due_ms, 8u);
 }
 
 // cts_tcp_senders_send_paced's planning: three launches, the middle one a single workgroup
@@ -684,6 +704,25 @@ __device__ __forceinline__ uint32_t tcp_exchange_limit(const cts_tcp_exchange_st
     code = CTS_TCP_SENDER_SENT;
     const uint64_t k = S.N - m;
     return k < (uint64_t)max_buffers ? (uint32_t)k : max_buffers;
+}
+
+// Entry e at position m takes t > 0 slots: the bytes it sends by direction; true = the sequence is complete. The only
+// step that knows how many slots a connection takes is the one that moves its entry: the bytes of buffers m .. m + t by
+// direction are the difference of two positions, whatever segment ends lie between, and the entry holds the position
+// at m (cts_tcp_exchange_init, _seek and this move keep it so).
+__device__ __forceinline__ bool tcp_exchange_move(cts_tcp_exchange_state* e, const ExchangeShape& S, uint64_t m,
+                                                  uint64_t t, uint64_t& bytes0, uint64_t& bytes1)
+{
+    uint64_t to[2];
+    exchange_position(S, m + t, to);
+    bytes0 = exchange_sub(to[0], e->bytes_sent[0]);
+    bytes1 = exchange_sub(to[1], e->bytes_sent[1]);
+    e->bytes_sent[0] += bytes0;
+    e->bytes_sent[1] += bytes1;
+    e->buffers_sent = m + t;
+    const bool ended = m + t == S.N;
+    if (ended) e->finished = 1u;
+    return ended;
 }
 
 }  // namespace
@@ -749,21 +788,9 @@ __global__ void __launch_bounds__(kBlock)
             no_room = 1u;
             code = CTS_TCP_SENDER_NO_ROOM;
         } else {
-            // the only step that knows how many slots a connection takes is the one that moves its entry: the bytes
-            // of buffers m .. m + t by direction are the difference of two positions, whatever segment ends lie
-            // between, and the entry holds the position at m (cts_tcp_exchange_init, _seek and this move keep it so)
-            cts_tcp_exchange_state* const e = entries + c;
-            uint64_t to[2];
-            exchange_position(S, m + t, to);
-            bytes0 = exchange_sub(to[0], e->bytes_sent[0]);
-            bytes1 = exchange_sub(to[1], e->bytes_sent[1]);
-            e->bytes_sent[0] += bytes0;
-            e->bytes_sent[1] += bytes1;
-            e->buffers_sent = m + t;
             buffers = (uint32_t)t;
             sent = 1u;
-            if (m + t == S.N) {
-                e->finished = 1u;
+            if (tcp_exchange_move(entries + c, S, m, t, bytes0, bytes1)) {
                 finished = 1u;
                 code = CTS_TCP_SENDER_FINISHED;
             }
@@ -787,13 +814,7 @@ __global__ void __launch_bounds__(kBlock)
     }
     apply_flush(words, bytes, red, wsum, ctr, sent_block, [&](uint32_t k) { return &tick->tick.buffers + k; },
                 &tick->tick.bytes);
-    if (threadIdx.x >= 8u && threadIdx.x < 10u) {
-        const uint32_t d = threadIdx.x - 8u;
-        uint64_t s = 0;
-#pragma unroll
-        for (int w = 0; w < kBlock / 64; ++w) s += dir[w][d];
-        if (s) atomicAdd((unsigned long long*)&tick->bytes_dir[d], (unsigned long long)s);
-    }
+    apply_flush_dir(dir, tick->bytes_dir, 8u);
 }
 
 // cts_tcp_exchange_send's planning: three launches, the middle one a single workgroup
@@ -811,6 +832,241 @@ hipError_t launch_tcp_exchange_plan(const uint32_t* conn_ids, uint32_t n, uint32
     tcp_exchange_apply<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, entries, n_conns, stride, capacity,
                                                                max_buffers, scratch.plain.sums, scratch.plain.prefix,
                                                                scratch.plain.before, codes, tick, sent_counters);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// The paced exchange tick (cts_tcp_exchange_send_paced): the exchange tick with every listed connection's wanted slots
+// cut by run_x of cts_tcp_exchange.h, the pace machine's walk with each step taken on the pace entry of the next
+// buffer's direction (entry c + d x n_conns: the side that sends direction d).
+//   tcp_exchange_paced_sums    the walk on register copies, nothing is stored
+//   tcp_exchange_paced_scan    the 64-byte tick block zeroed and its next_due_ms set to INT64_MAX
+//   tcp_exchange_paced_apply   the walk again, p_i, t_i, the codes, the entry's move (tcp_exchange_move), the pace
+//                              entries' updates, the tick with bytes_dir and the tail, the sent block
+// The walk pays exchange_element's division once: an ExchangeCursor is seeded at m and moved by additions. A lane keeps
+// both directions' pace registers, `cur` for the next buffer's direction and `oth`, and swaps them when the direction
+// flips, so no register is ever indexed by a direction. tcp_exchange_descs and the fill follow unchanged: they read
+// prefix, before and the block's first 32 bytes.
+
+static_assert(sizeof(cts_tcp_exchange_paced_tick) == 64 && offsetof(cts_tcp_exchange_paced_tick, next_due_ms) == 48 &&
+                  offsetof(cts_tcp_exchange_paced_tick, connections_waiting) == 56,
+              "cts_tcp_exchange_paced_tick: an exchange tick and the paced tick's 16-byte tail");
+
+namespace {
+
+// A listed connection's two pace entries in registers. two = the pattern sends both ways (PushPull, Duplex); a one-way
+// pattern never loads, moves or saves `oth`, whose registers stay zero.
+struct ExchangePace {
+    PaceRegs cur, oth;
+    ExchangeCursor at;
+    bool two;
+
+    __device__ __forceinline__ void load(const cts_tcp_sender_pace* __restrict__ pace, uint32_t c, uint32_t n_conns,
+                                         const ExchangeShape& S, uint64_t m)
+    {
+        at.seed(S, m);
+        two = S.pattern >= CTS_TCP_EXCHANGE_PUSHPULL;
+        cur.load(pace + ((uint64_t)c + (uint64_t)at.d * n_conns));
+        if (two) oth.load(pace + ((uint64_t)c + (uint64_t)(at.d ^ 1u) * n_conns));
+    }
+    __device__ __forceinline__ void save(cts_tcp_sender_pace* __restrict__ pace, uint32_t c, uint32_t n_conns) const
+    {
+        cur.save(pace + ((uint64_t)c + (uint64_t)at.d * n_conns));
+        if (two) oth.save(pace + ((uint64_t)c + (uint64_t)(at.d ^ 1u) * n_conns));
+    }
+    __device__ __forceinline__ bool unpaced() const { return cur.unpaced() && (!two || oth.unpaced()); }
+
+    // run_x(cap) of cts_tcp_exchange.h; cap <= N - m. PaceRegs::run's loop with the size and the entry taken from the
+    // cursor. A wave takes as long as its longest lane.
+    __device__ __forceinline__ uint32_t run(int64_t now, uint32_t cap, const ExchangeShape& S)
+    {
+        uint32_t count = 0;
+        while (count < cap) {
+            const uint32_t size = at.len(S);
+            if (cur.pending != 0u) {
+                if (now < cur.due) break;
+                cur.pending = 0u;
+            } else {
+                const int64_t off = cur.step(now, (int64_t)size);
+                if (off > 0) {
+                    cur.pending = 1u;
+                    cur.due = now + off;
+                    break;
+                }
+            }
+            ++count;
+            if (at.advance(S, size)) {
+                const PaceRegs was = cur;
+                cur = oth;
+                oth = was;
+            }
+        }
+        return count;
+    }
+};
+
+// Listed connection c's wanted slots at now_ms: the limit, or run_x(limit) on X, register copies of its pace entries.
+// paced = X holds the entries and has been moved.
+__device__ __forceinline__ uint32_t tcp_exchange_paced_want(const cts_tcp_exchange_state* __restrict__ entries,
+                                                            const cts_tcp_sender_pace* __restrict__ pace, uint32_t c,
+                                                            uint32_t n_conns, uint32_t stride, uint32_t max_buffers,
+                                                            int64_t now, uint32_t& code, ExchangeShape& S, uint64_t& m,
+                                                            ExchangePace& X, bool& paced)
+{
+    paced = false;
+    const uint32_t limit = tcp_exchange_limit(entries, c, n_conns, stride, max_buffers, code, S, m);
+    if (code != CTS_TCP_SENDER_SENT) return 0u;
+    X.load(pace, c, n_conns, S, m);
+    if (X.unpaced()) return limit;
+    paced = true;
+    return X.run(now, limit, S);
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(kBlock)
+    tcp_exchange_paced_sums(const uint32_t* __restrict__ ids, uint32_t n,
+                            const cts_tcp_exchange_state* __restrict__ entries,
+                            const cts_tcp_sender_pace* __restrict__ pace, uint32_t n_conns, uint32_t stride,
+                            uint32_t max_buffers, int64_t now, uint64_t* __restrict__ sums)
+{
+    __shared__ uint64_t wsum[kBlock / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
+    uint64_t want = 0;
+    if (i < n) {
+        uint32_t code;
+        ExchangeShape S{};
+        uint64_t m;
+        ExchangePace X{};
+        bool paced;
+        want = tcp_exchange_paced_want(entries, pace, ids[i], n_conns, stride, max_buffers, now, code, S, m, X, paced);
+    }
+    tile_sum_store(want, wsum, sums);
+}
+
+// One workgroup. tick is 16 dwords (cts_tcp_exchange_paced_tick); its next_due_ms starts at INT64_MAX.
+__global__ void __launch_bounds__(kBlock)
+    tcp_exchange_paced_scan(uint64_t* __restrict__ sums, uint64_t tiles, uint64_t* __restrict__ prefix_total,
+                            uint32_t* __restrict__ tick)
+{
+    __shared__ uint64_t wsum[kBlock / 64];
+    const uint64_t total = tile_sums_scan(sums, tiles, wsum);
+    if (threadIdx.x == 0u) *prefix_total = total;
+    constexpr uint32_t kDue = offsetof(cts_tcp_exchange_paced_tick, next_due_ms) / 4u;
+    if (threadIdx.x < sizeof(cts_tcp_exchange_paced_tick) / 4u)
+        tick[threadIdx.x] = threadIdx.x == kDue ? 0xFFFFFFFFu : threadIdx.x == kDue + 1u ? 0x7FFFFFFFu : 0u;
+}
+
+__global__ void __launch_bounds__(kBlock)
+    tcp_exchange_paced_apply(const uint32_t* __restrict__ ids, uint32_t n,
+                             cts_tcp_exchange_state* __restrict__ entries, cts_tcp_sender_pace* __restrict__ pace,
+                             uint32_t n_conns, uint32_t stride, uint32_t capacity, uint32_t max_buffers, int64_t now,
+                             const uint64_t* __restrict__ sums, uint64_t* __restrict__ prefix,
+                             uint64_t* __restrict__ before, uint32_t* __restrict__ codes,
+                             cts_tcp_exchange_paced_tick* __restrict__ tick, uint64_t* __restrict__ sent_block)
+{
+    __shared__ uint64_t wsum[kBlock / 64];
+    __shared__ uint64_t ctr[kBlock / 64][kCounterCount];
+    __shared__ uint32_t red[kBlock / 64][7];
+    __shared__ uint64_t dir[kBlock / 64][2];
+    __shared__ int64_t due[kBlock / 64];
+    zero_counters<kBlock / 64>(ctr);
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
+    uint32_t code = CTS_TCP_SENDER_SENT, c = 0u;
+    uint64_t want = 0, m = 0;
+    ExchangeShape S{};
+    ExchangePace X{};
+    bool paced = false;
+    if (i < n) {
+        c = ids[i];
+        want = tcp_exchange_paced_want(entries, pace, c, n_conns, stride, max_buffers, now, code, S, m, X, paced);
+    }
+    uint64_t total;
+    const uint64_t p = sums[blockIdx.x] + tile_scan_exclusive(want, wsum, total);
+    uint64_t bytes0 = 0, bytes1 = 0;
+    int64_t my_due = kNoDue;
+    uint32_t buffers = 0, sent = 0, finished = 0, no_room = 0, skipped = 0, waiting = 0, pending = 0;
+    if (i < n) {
+        prefix[i] = p;
+        const uint64_t pc = p < (uint64_t)capacity ? p : (uint64_t)capacity;
+        const uint64_t t = want < (uint64_t)capacity - pc ? want : (uint64_t)capacity - pc;
+        if (code != CTS_TCP_SENDER_SENT) {
+            skipped = 1u;
+        } else if (want == 0u) {
+            // pacing lets nothing out: the entry stays, the next direction's pace entry may hold a new pending task
+            waiting = 1u;
+            code = CTS_TCP_SENDER_WAITING;
+            X.save(pace, c, n_conns);
+        } else if (t == 0u) {
+            no_room = 1u;
+            code = CTS_TCP_SENDER_NO_ROOM;
+            if (paced) X.load(pace, c, n_conns, S, m);  // all three entries stay: what counts below is what is stored
+        } else {
+            if (paced) {
+                if (t < want) {  // cut by the capacity: the machine moves t steps from the stored entries
+                    X.load(pace, c, n_conns, S, m);
+                    (void)X.run(now, (uint32_t)t, S);
+                }
+                X.save(pace, c, n_conns);
+            }
+            buffers = (uint32_t)t;
+            sent = 1u;
+            if (tcp_exchange_move(entries + c, S, m, t, bytes0, bytes1)) {
+                finished = 1u;
+                code = CTS_TCP_SENDER_FINISHED;
+            }
+        }
+        if (skipped == 0u) {
+            // a connection counts once; of a table kept by this tick only the next buffer's entry can be pending
+            if (X.cur.pending != 0u) my_due = X.cur.due;
+            if (X.oth.pending != 0u && X.oth.due < my_due) my_due = X.oth.due;
+            pending = (X.cur.pending | X.oth.pending) != 0u ? 1u : 0u;
+        }
+        before[i] = m;
+        if (codes != nullptr) codes[i] = code;
+    }
+    bytes0 = wave_sum64(bytes0);
+    bytes1 = wave_sum64(bytes1);
+    const uint64_t bytes = bytes0 + bytes1;
+    // buffers, connections_sent, _finished, _no_room, _skipped; then the tail's connections_waiting, _pending
+    const uint32_t words[7] = {wave_sum(buffers), wave_sum(sent),    wave_sum(finished), wave_sum(no_room),
+                               wave_sum(skipped), wave_sum(waiting), wave_sum(pending)};
+    my_due = wave_min64(my_due);
+    if ((threadIdx.x & 63u) == 0u) {
+        uint64_t* const own = ctr[threadIdx.x >> 6];
+        own[0] = bytes;     // cts_counters_sent.bytes_sent (TcpStatusDetails.m_bytesSent of whichever side sent)
+        own[1] = words[0];  // .buffers_sent
+        own[2] = words[2];  // .connections_finished
+        dir[threadIdx.x >> 6][0] = bytes0;
+        dir[threadIdx.x >> 6][1] = bytes1;
+        due[threadIdx.x >> 6] = my_due;
+    }
+    apply_flush(
+        words, bytes, red, wsum, ctr, sent_block,
+        [&](uint32_t k) { return k < 5u ? &tick->tick.tick.buffers + k : &tick->connections_waiting + (k - 5u); },
+        &tick->tick.tick.bytes);
+    apply_flush_dir(dir, tick->tick.bytes_dir, 8u);
+    apply_flush_due(due, &tick->next_due_ms, 10u);
+}
+
+// cts_tcp_exchange_send_paced's planning: three launches, the middle one a single workgroup
+hipError_t launch_tcp_exchange_paced_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
+                                          cts_tcp_exchange_state* entries, cts_tcp_sender_pace* pace,
+                                          uint32_t n_conns, int64_t now_ms, uint32_t stride, uint32_t capacity,
+                                          uint32_t* codes, cts_tcp_exchange_paced_tick* tick, uint64_t* sent_counters,
+                                          const TcpExchangePacedScratch& scratch, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    const uint64_t tiles = plan_tiles(n);
+    const TcpSenderScratch& plain = scratch.exchange.plain;
+    tcp_exchange_paced_sums<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, entries, pace, n_conns, stride,
+                                                                    max_buffers, now_ms, plain.sums);
+    tcp_exchange_paced_scan<<<1, kBlock, 0, stream>>>(plain.sums, tiles, plain.prefix + n,
+                                                      reinterpret_cast<uint32_t*>(tick));
+    tcp_exchange_paced_apply<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, entries, pace, n_conns, stride,
+                                                                     capacity, max_buffers, now_ms, plain.sums,
+                                                                     plain.prefix, plain.before, codes, tick,
+                                                                     sent_counters);
     return hipGetLastError();
 }
 

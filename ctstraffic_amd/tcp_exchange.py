@@ -6,6 +6,10 @@ sequence; one :func:`exchange_send` writes up to ``max_buffers`` of them for eve
 arena slots, with their descriptors. The receiver of direction d of connection c is slot ``c + d * n_conns`` of
 receiver tables of ``2 * n_conns`` slots, and the receive half (Engine.verify with a base_index, Engine.refview_conns,
 Engine.conns_close) runs over the descriptors unchanged. The model of a tick is workload.tcp_exchange_view.
+
+Send pacing for every pattern is :func:`exchange_send_paced` over a pace table of ``2 * n_conns`` 64-byte entries
+(types.TCP_SENDER_PACE_DTYPE, made by tcp_senders.pace_init), entry ``c + d * n_conns`` for the side that sends
+direction d; :class:`PacedExchangeTable` holds one. Its model is workload.tcp_paced_exchange_view.
 """
 from __future__ import annotations
 
@@ -14,7 +18,8 @@ import ctypes
 import numpy as np
 
 from ._lib import check, lib
-from .types import DESC_DTYPE, TCP_EXCHANGE_DTYPE, TCP_EXCHANGE_TICK_DTYPE
+from .types import (DESC_DTYPE, TCP_EXCHANGE_DTYPE, TCP_EXCHANGE_PACED_TICK_DTYPE, TCP_EXCHANGE_TICK_DTYPE,
+                    TCP_SENDER_PACE_DTYPE)
 
 
 def _one(entry) -> np.ndarray:
@@ -73,6 +78,28 @@ def exchange_send(engine, arena, stride: int, first_slot: int, capacity: int, co
               capacity, _ptr(conn_ids), n, max_buffers, _ptr(entries), n_conns, _ptr(descs), _ptr(codes), _ptr(tick),
               _ptr(sent_counters), _ptr(scratch), _nbytes(scratch) if scratch_bytes is None else scratch_bytes,
               _stream(stream)))
+
+
+def exchange_paced_scratch_bytes(n: int) -> int:
+    """cts_tcp_exchange_paced_scratch_bytes: the scratch a paced tick over n listed connections needs."""
+    return int(lib().cts_tcp_exchange_paced_scratch_bytes(n))
+
+
+def exchange_send_paced(engine, arena, stride: int, first_slot: int, capacity: int, conn_ids, max_buffers: int,
+                        entries, pace, n_conns: int, now_ms: int, descs, scratch, codes=None, tick=None,
+                        sent_counters=None, stream=None, n: int = None, arena_bytes: int = None,
+                        scratch_bytes: int = None) -> None:
+    """cts_tcp_exchange_send_paced: :func:`exchange_send` at the time now_ms over the pace table `pace` (64 bytes per
+    side: 2 x n_conns entries); tick is 64 bytes or None. Raises CtsError(CTS_E_INVALID) for a refused argument."""
+    from .engine import _nbytes, _ptr, _stream
+
+    n = _nbytes(conn_ids) // 4 if n is None else n
+    check("cts_tcp_exchange_send_paced",
+          engine._L.cts_tcp_exchange_send_paced(
+              engine._h, _ptr(arena), _nbytes(arena) if arena_bytes is None else arena_bytes, stride, first_slot,
+              capacity, _ptr(conn_ids), n, max_buffers, _ptr(entries), _ptr(pace), n_conns, now_ms, _ptr(descs),
+              _ptr(codes), _ptr(tick), _ptr(sent_counters), _ptr(scratch),
+              _nbytes(scratch) if scratch_bytes is None else scratch_bytes, _stream(stream)))
 
 
 class ExchangeTable:
@@ -152,3 +179,67 @@ class ExchangeTable:
 
     def read_sent(self, stream=None) -> dict:
         return self.engine.read_counters_sent(self.sent, stream=stream)
+
+
+class PacedExchangeTable(ExchangeTable):
+    """An ExchangeTable with a pace entry per side of every connection slot and the paced tick.
+
+    pace_settings: per connection slot a pair (client, server) of dicts of tcp_senders.pace_init's keywords
+    (bytes_per_second, period_ms, burst_count, burst_delay_ms; {} = unpaced): the client's pace direction 0, the
+    server's direction 1. The pace table has 2 x n_conns entries, entry ``c + d * n_conns`` for direction d. Every
+    first quantum starts at start_ms. ``send(conn_ids, max_buffers, now_ms)`` is one paced tick; the plain tick stays
+    available as ``ExchangeTable.send(table, ...)`` over the same entries."""
+
+    def __init__(self, engine, settings, pace_settings, stride: int, capacity: int, start_ms: int = 0, **kw):
+        import torch
+
+        from .tcp_senders import pace_init
+
+        super().__init__(engine, settings, stride, capacity, **kw)
+        if len(pace_settings) != self.n_conns:
+            raise ValueError("%d pace settings for a table of %d" % (len(pace_settings), self.n_conns))
+        self.fresh_pace = np.zeros(2 * self.n_conns, dtype=TCP_SENDER_PACE_DTYPE)
+        for c, sides in enumerate(pace_settings):
+            for d in (0, 1):
+                self.fresh_pace[c + d * self.n_conns] = pace_init(start_ms=start_ms, **sides[d])
+        words = max(1, 2 * self.n_conns) * (TCP_SENDER_PACE_DTYPE.itemsize // 8)
+        self.pace = torch.zeros(words, dtype=torch.int64, device=self.device)
+        self.load_pace(self.fresh_pace)
+        self.scratch = torch.zeros((exchange_paced_scratch_bytes(self.max_listed) + 7) // 8, dtype=torch.int64,
+                                   device=self.device)
+        self.tick = torch.zeros(TCP_EXCHANGE_PACED_TICK_DTYPE.itemsize // 8, dtype=torch.int64, device=self.device)
+
+    def send(self, conn_ids, max_buffers: int, now_ms: int, first_slot: int = 0, stream=None,
+             capacity: int = None) -> None:
+        """One paced tick of conn_ids (uint32/int32 device tensor, distinct, at most max_listed of them) at now_ms."""
+        from .engine import _nbytes
+
+        n = _nbytes(conn_ids) // 4
+        if n > self.codes.numel():
+            raise ValueError("%d ids listed, the table's codes and scratch hold %d" % (n, self.codes.numel()))
+        capacity = self.capacity if capacity is None else capacity
+        if capacity > self.capacity:
+            raise ValueError("capacity %d, the table's descriptors hold %d" % (capacity, self.capacity))
+        exchange_send_paced(self.engine, self.arena, self.stride, first_slot, capacity, conn_ids, max_buffers,
+                            self.entries, self.pace, self.n_conns, now_ms, self.descs, self.scratch, codes=self.codes,
+                            tick=self.tick, sent_counters=self.sent, stream=stream)
+
+    def load_pace(self, pace: np.ndarray) -> None:
+        """Write pace (TCP_SENDER_PACE_DTYPE[2 x n_conns]) over the pace table."""
+        import torch
+
+        q = np.ascontiguousarray(pace, dtype=TCP_SENDER_PACE_DTYPE)
+        if len(q) != 2 * self.n_conns:
+            raise ValueError("%d pace entries for a table of %d connections" % (len(q), self.n_conns))
+        if self.n_conns:
+            self.pace.copy_(torch.from_numpy(q.view(np.int64).copy()))
+
+    def read(self):
+        """(entries, codes uint32, tick: one TCP_EXCHANGE_PACED_TICK_DTYPE record) copied to the host."""
+        return (self.entries.cpu().numpy().view(TCP_EXCHANGE_DTYPE)[: self.n_conns],
+                self.codes.cpu().numpy().view(np.uint32),
+                self.tick.cpu().numpy().view(TCP_EXCHANGE_PACED_TICK_DTYPE)[0])
+
+    def read_pace(self) -> np.ndarray:
+        """The pace table (TCP_SENDER_PACE_DTYPE[2 x n_conns]) copied to the host."""
+        return self.pace.cpu().numpy().view(TCP_SENDER_PACE_DTYPE)[: 2 * self.n_conns]

@@ -226,3 +226,10 @@ TCP_EXCHANGE_PUSH, TCP_EXCHANGE_PULL, TCP_EXCHANGE_PUSHPULL, TCP_EXCHANGE_DUPLEX
 # cts_tcp_exchange_tick: what one cts_tcp_exchange_send did; its first 32 bytes are a cts_tcp_sender_tick
 TCP_EXCHANGE_TICK_DTYPE = np.dtype(TCP_SENDER_TICK_DTYPE.descr + [("bytes_dir", "<u8", (2,))])
 assert TCP_EXCHANGE_DTYPE.itemsize == 64 and TCP_EXCHANGE_TICK_DTYPE.itemsize == 48
+# cts_tcp_exchange_paced_tick: what one cts_tcp_exchange_send_paced did; its first 48 bytes are a cts_tcp_exchange_tick,
+# its tail is the paced senders' tick's
+TCP_EXCHANGE_PACED_TICK_DTYPE = np.dtype(
+    TCP_EXCHANGE_TICK_DTYPE.descr + [("next_due_ms", "<i8"), ("connections_waiting", "<u4"),
+                                     ("connections_pending", "<u4")]
+)
+assert TCP_EXCHANGE_PACED_TICK_DTYPE.itemsize == 64

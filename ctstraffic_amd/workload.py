@@ -1284,6 +1284,13 @@ def tcp_exchange_view(entries: np.ndarray, stride: int, arena: np.ndarray, first
     tick's buffers (the only Python loop runs over the distinct buffer lengths). arena, descs (what dev_descs held
     before, default zeros) and counters (the sent block before, default zeros) are not modified; the results are
     copies."""
+    return _tcp_exchange_tick(entries, stride, arena, first_slot, capacity, ids, max_buffers, descs, counters, None)
+
+
+def _tcp_exchange_tick(entries, stride, arena, first_slot, capacity, ids, max_buffers, descs, counters, cut):
+    """tcp_exchange_view's tick. cut (None for the plain tick): cut(i, c, limit, entry) -> the slots that listed
+    connection i (slot c, running, wanting `limit`, entry = its record) wants after pacing; a running connection cut
+    to 0 gets code 5."""
     from .types import TCP_EXCHANGE_DTYPE
 
     u = np.uint64
@@ -1300,6 +1307,11 @@ def tcp_exchange_view(entries: np.ndarray, stride: int, arena: np.ndarray, first
     ended = ~skipped & ((E["finished"] != 0) | (m0 >= N))
     running = ~skipped & ~ended
     w = np.where(running, np.minimum(N - np.minimum(m0, N), u(max_buffers)), u(0))
+    waiting = np.zeros(n, dtype=bool)
+    if cut is not None:
+        for i in np.nonzero(running)[0]:
+            w[i] = cut(int(i), int(c[i]), int(w[i]), E[i])
+        waiting = running & (w == 0)
     p = np.concatenate([np.zeros(1, dtype=u), np.cumsum(w, dtype=u)])[:n]
     cap = u(capacity)
     t = np.minimum(w, cap - np.minimum(p, cap))
@@ -1307,6 +1319,7 @@ def tcp_exchange_view(entries: np.ndarray, stride: int, arena: np.ndarray, first
     finished = took & (m0 + t == N)
     codes = np.zeros(n, dtype=np.uint32)
     codes[skipped], codes[ended], codes[running & (t == 0)], codes[finished] = 4, 2, 3, 1
+    codes[waiting] = 5
     total = int(t.sum())
     # the buffers: listed connection `owner` of tick-local slot g, its buffer j, element m of its sequence
     owner = np.repeat(np.arange(n, dtype=np.int64), t.astype(np.int64))
@@ -1316,7 +1329,8 @@ def tcp_exchange_view(entries: np.ndarray, stride: int, arena: np.ndarray, first
     offset = pos & u(PATTERN_PERIOD - 1)
     by_dir = [int(length[d == u(k)].sum()) for k in (0, 1)]
     tick = {"bytes": sum(by_dir), "buffers": total, "connections_sent": int(took.sum()),
-            "connections_finished": int(finished.sum()), "connections_no_room": int((running & (t == 0)).sum()),
+            "connections_finished": int(finished.sum()),
+            "connections_no_room": int((running & (t == 0) & ~waiting).sum()),
             "connections_skipped": int((skipped | ended).sum()), "bytes_dir": by_dir}
     out_descs = np.zeros(capacity, dtype=DESC_DTYPE) if descs is None else np.array(descs, dtype=DESC_DTYPE, copy=True)
     dd = out_descs[:total]
@@ -1341,3 +1355,108 @@ def tcp_exchange_view(entries: np.ndarray, stride: int, arena: np.ndarray, first
     after["buffers_sent"] += total
     after["connections_finished"] += tick["connections_finished"]
     return TcpExchangeTickView(out, out_descs, codes, tick, after, e, p, t, d)
+
+
+# ---- send pacing for every pattern (cts_tcp_exchange_send_paced) ----------------------------------------------------
+def tcp_exchange_pace_entries(pace_settings, start_ms: int = 0):
+    """The pace table of cts_tcp_exchange_send_paced as a model: pace_settings is, per connection slot, a pair (client,
+    server) of tcp_sender_pace_entries' dicts. Returns TCP_SENDER_PACE_DTYPE[2 x n_conns], entry c + d x n_conns for
+    the side that sends direction d."""
+    n_conns = len(pace_settings)
+    return tcp_sender_pace_entries([pace_settings[c][d] for d in (0, 1) for c in range(n_conns)], start_ms)
+
+
+def _pace_unpaced(q: dict) -> bool:
+    return q["bytes_per_quantum"] <= 0 and q["burst_count"] == 0 and not q["pending"]
+
+
+def _pace_run_x(Q: dict, now: int, cap: int, elements) -> int:
+    """run_x(cap) of include/cts_tcp_exchange.h: Q = {direction: pace entry as a dict} (moved in place), elements(k) =
+    (direction, length) of the k-th buffer from the connection's position."""
+    count = 0
+    while count < cap:
+        d, size = elements(count)
+        q = Q[d]
+        if q["pending"]:
+            if now < q["due_ms"]:
+                break
+            q["pending"] = 0
+        else:
+            off = _pace_step(q, now, size)
+            if off > 0:
+                q["pending"], q["due_ms"] = 1, now + off
+                break
+        count += 1
+    return count
+
+
+@dataclass
+class TcpPacedExchangeTickView(TcpExchangeTickView):
+    """What one cts_tcp_exchange_send_paced leaves behind (tcp_paced_exchange_view): a TcpExchangeTickView (codes with
+    5 = waiting), and"""
+    pace: np.ndarray = None     # TCP_SENDER_PACE_DTYPE[2 x n_conns] after the tick
+    waiting: np.ndarray = None  # the listed positions with code 5
+    tail: dict = None           # TCP_SENDER_PACED_TAIL_FIELDS
+    wanted: np.ndarray = None   # uint64 per listed id: w, the slots pacing lets it want
+
+
+def tcp_paced_exchange_view(entries: np.ndarray, pace: np.ndarray, now_ms: int, stride: int, arena: np.ndarray,
+                            first_slot: int, capacity: int, ids, max_buffers: int, descs: np.ndarray = None,
+                            counters: dict = None) -> TcpPacedExchangeTickView:
+    """One tick of cts_tcp_exchange_send_paced as a model: tcp_exchange_view with every running listed connection's
+    wanted slots cut by run_x(limit) over its two pace entries (a plain Python loop per paced connection, in Python
+    integers), the pace entries moved as the header states (run_x(limit), or run_x(t) from the stored entries for the
+    one connection the capacity cuts; untouched with code 3), and the tick's tail. pace has 2 x len(entries) records,
+    entry c + d x n_conns for direction d. Nothing passed in is modified."""
+    from .types import TCP_SENDER_PACE_DTYPE
+
+    q_out = np.array(pace, dtype=TCP_SENDER_PACE_DTYPE, copy=True)
+    n_conns = len(entries)
+    if len(q_out) != 2 * n_conns:
+        raise ValueError("%d pace entries beside %d exchange entries" % (len(q_out), n_conns))
+    moved, asked = {}, {}
+
+    def stored(c, dirs):
+        return {d: {f: int(q_out[c + d * n_conns][f]) for f in _PACE_SCALARS} for d in dirs}
+
+    def cut(i, c, limit, E):
+        pattern, T, B = int(E["pattern"]), int(E["transfer_bytes"]), int(E["buffer_size"])
+        P, Q_, m = int(E["push_bytes"]), int(E["pull_bytes"]), int(E["buffers_sent"])
+        dirs = {0: (0,), 1: (1,)}.get(pattern, (0, 1))
+
+        def elements(k):
+            d, _, length, _ = tcp_exchange_element(pattern, T, B, P, Q_, m + k)
+            return d, length
+
+        Q = stored(c, dirs)
+        if all(_pace_unpaced(q) for q in Q.values()):
+            w = limit  # unpaced: no step moves an entry or defers a send (a limit of 2^31 is no loop)
+        else:
+            w = _pace_run_x(Q, now_ms, limit, elements)
+        moved[i], asked[i] = Q, (c, dirs, elements, w)
+        return w
+
+    v = _tcp_exchange_tick(entries, stride, arena, first_slot, capacity, ids, max_buffers, descs, counters, cut)
+    wanted = np.zeros(len(v.codes), dtype=np.uint64)
+    due = []
+    for i, (c, dirs, elements, w) in asked.items():  # q_out still holds c's entries from before: the ids are distinct
+        t, code = int(v.taken[i]), int(v.codes[i])
+        wanted[i] = w
+        if code == 3:       # no room: the stored entries stay
+            Q = stored(c, dirs)
+        elif 0 < t < w:     # cut by the capacity: t steps, and no task beyond the t-th
+            Q = stored(c, dirs)
+            if _pace_run_x(Q, now_ms, t, elements) != t:
+                raise AssertionError("run_x(t) stopped before t")
+        else:               # code 5 (w == 0), or everything it wanted
+            Q = moved[i]
+        for d, q in Q.items():
+            for f in ("bytes_this_quantum", "quantum_start_ms", "due_ms", "burst_left", "pending"):
+                q_out[c + d * n_conns][f] = q[f]
+        pending = [q["due_ms"] for q in Q.values() if q["pending"]]
+        if pending:         # a connection counts once
+            due.append(min(pending))
+    tail = {"next_due_ms": min(due) if due else TCP_SENDER_NO_DUE, "connections_waiting": int((v.codes == 5).sum()),
+            "connections_pending": len(due)}
+    return TcpPacedExchangeTickView(v.arena, v.descs, v.codes, v.tick, v.counters, v.entries, v.prefix, v.taken,
+                                    v.direction, q_out, np.nonzero(v.codes == 5)[0], tail, wanted)

@@ -30,6 +30,14 @@
  *                                                               whichever side sends them: the arena's bytes, their
  *                                                               descriptors, the entries, a tick block
  *
+ * Send pacing (-RateLimit, -BurstCount / -BurstDelay; cts_tcp_senders.h) runs in the tick for every pattern:
+ *
+ *   per tick   cts_tcp_exchange_send_paced(..., dev_pace, now_ms, ...)  -> the same, but every listed connection sends
+ *                                                               what CreateNewTask's send branch of the side whose turn
+ *                                                               it is lets out at now_ms, from two 64-byte pace entries
+ *                                                               per connection; the tick block ends with the time of
+ *                                                               the next deferred send
+ *
  * The receiving half consumes the descriptors unchanged (cts_verify_at, cts_refview_accumulate_conns, cts_conns_close
  * of cts_connections.h) over receiver tables of 2 x n_conns slots: the receiver of direction d of connection c is slot
  * c + d x n_conns, the direction-0 receivers (the servers) first, then the direction-1 receivers (the clients).
@@ -39,7 +47,7 @@
  * likewise writes ahead of its verification; what orders the two halves is the stream.
  *
  * Out of scope:
- *   - send pacing: cts_tcp_senders_send_paced stays Push-only
+ *   - closed forms for the runs of sends inside a quantum: the paced tick walks a paced connection's buffers one by one
  *   - -Buffer:[lo,hi] random buffer sizes: an entry has one buffer_size
  *   - a ring that wraps: a tick writes the slots first_slot .. first_slot + total of one flat arena
  *   - the connection-id and completion messages that frame a TCP connection (ctsIOPattern.cpp:330-470)
@@ -153,6 +161,87 @@ int cts_tcp_exchange_send(cts_engine* engine, void* dev_arena, uint64_t arena_by
                           uint32_t max_buffers, cts_tcp_exchange_state* dev_entries, uint32_t n_conns,
                           cts_buf_desc* dev_descs, uint32_t* dev_codes, cts_tcp_exchange_tick* dev_tick,
                           void* dev_sent_counters, void* dev_scratch, size_t scratch_bytes, void* stream);
+
+/* ---- send pacing ---------------------------------------------------------------------------------------------------
+ * What one paced tick did. 64 bytes, 8-byte aligned. Its first 48 bytes are the plain exchange tick's block, its tail
+ * is cts_tcp_sender_paced_tick's. */
+typedef struct cts_tcp_exchange_paced_tick {
+    cts_tcp_exchange_tick tick;
+    int64_t next_due_ms;          /* the smallest due_ms among the listed running connections (codes 0, 1, 3 and 5) that
+                                     the tick leaves with a pending send; INT64_MAX when there is none */
+    uint32_t connections_waiting; /* code 5 */
+    uint32_t connections_pending; /* the listed running connections left with a pending send, each counted once */
+} cts_tcp_exchange_paced_tick;
+
+/* Bytes of dev_scratch a paced tick over n listed connections needs (the plain tick's, with the larger tick block). */
+size_t cts_tcp_exchange_paced_scratch_bytes(uint32_t n);
+
+/* One paced tick at the time now_ms: cts_tcp_exchange_send, with every listed running connection's wanted slots cut to
+ * what pacing lets out.
+ *
+ * The pace table: dev_pace holds 2 x n_conns cts_tcp_sender_pace entries (cts_tcp_sender_pace_init). Entry c + d x
+ * n_conns is the pacing state of the side that sends direction d of connection c, the client for d = 0, the server for
+ * d = 1: the receivers' indexing. Each side of a reference connection is a ctsIoPattern of its own with its own
+ * m_bytesSendingThisQuantum, m_quantumStartTimeMs and m_burstCount. Push uses entry c only, Pull entry c + n_conns
+ * only, PushPull and Duplex both; the entries a pattern does not use are never read or written.
+ *
+ * The walk: with limit = min(max_buffers, N - E.buffers_sent), m = E.buffers_sent and step(Q, now, size) the step of
+ * cts_tcp_senders.h (CreateNewTask's send branch, ctsIOPattern.cpp:593-674) over the pace entry Q,
+ *
+ *   run_x(cap):  count = 0
+ *     while count < cap:
+ *         (d, len) = element m + count of the sequence;  Q = dev_pace[c + d x n_conns]
+ *         if Q.pending:  if now_ms < Q.due_ms: break;  Q.pending = 0            the waiting send goes out first
+ *         else:          off = step(Q, now_ms, len)
+ *                        if off > 0: Q.pending = 1; Q.due_ms = now_ms + off; break   task created, send deferred
+ *         count += 1
+ *     return count
+ *
+ * which is run() of cts_tcp_senders.h with every step taken on the pace entry of the next buffer's direction. The
+ * connection wants w = run_x(limit) slots; p and t are the plain tick's:
+ *   w == 0                       nothing sent (code 5, CTS_TCP_SENDER_WAITING), E untouched, the pace entries as
+ *                                run_x(limit) leaves them (a first step may have created the pending task)
+ *   w > 0, t == 0                nothing sent (code 3), E and both pace entries untouched
+ *   0 < t < w                    t buffers sent, the pace entries as run_x(t) from the stored entries leaves them (no
+ *                                task beyond the t-th is created)
+ *   t == w                       w buffers sent, the pace entries as run_x(limit) leaves them
+ * Codes 0-4, the buffers' bytes, the descriptors (receiver c + d x n_conns), E's move, bytes_dir, the sent block and
+ * the no-gap rule are cts_tcp_exchange_send's; tick.buffers = min(capacity, sum of w). Connections with codes 2 and 4
+ * have no pace entry read, and do not count for next_due_ms or connections_pending.
+ *
+ * A deferred buffer holds the connection's sequence: nothing after it goes out before it. So of a connection's two
+ * pace entries at most one is ever pending, the one of the next buffer's direction, and next_due_ms and
+ * connections_pending count a connection once, with that entry's due_ms. (Should a caller's table hold both pending,
+ * the connection still counts once, with the smaller due_ms.)
+ *
+ * Duplex: as the interleaving of the two directions is fixed (buffer m has d = m & 1), a deferred buffer also holds the
+ * other direction's next buffer, which the reference's other side, a pattern of its own, could send meanwhile. No send
+ * leaves earlier than the reference's CreateNewTask on that side would release it; a send may leave later. Per side,
+ * the calls to step (their times and sizes) are what the reference's side would see if asked at those times. The same
+ * holds at a PushPull segment end, where the reference waits for the segment anyway.
+ *
+ * Two equalities:
+ *   - a table whose used pace entries all have bytes_per_quantum == 0, burst_count == 0 and pending == 0 gives what
+ *     cts_tcp_exchange_send gives, byte for byte and field for field, with the tail {INT64_MAX, 0, 0}. Such a
+ *     connection is not walked: max_buffers = 2^31 is no loop.
+ *   - a table of Push entries gives what cts_tcp_senders_send_paced gives over the same transfers and pace settings:
+ *     the arena, the descriptors, the codes, the pace entries [0, n_conns), the tick's first 32 bytes, its three tail
+ *     fields and the sent block.
+ *
+ * Arguments: cts_tcp_exchange_send's, and dev_pace non-null when n_conns != 0 and 8-byte aligned, 2 x n_conns entries;
+ * now_ms >= 0; dev_tick (may be NULL) a cts_tcp_exchange_paced_tick; scratch_bytes >=
+ * cts_tcp_exchange_paced_scratch_bytes(n). CTS_E_INVALID otherwise, nothing launched; n == 0 is CTS_OK. The caller's
+ * duties are the paced senders' tick's: now_ms does not decrease from tick to tick of a table and stays below 2^62,
+ * bytes_per_quantum x the quanta a tick skips fits an int64, and a pace entry comes from cts_tcp_sender_pace_init.
+ * Outside them, or with an entry that cts_tcp_exchange_init or _seek did not make, the values of the pace entries, the
+ * wanted counts, the lengths and the tick's tail are unspecified, but no write leaves the entries, the capacity's
+ * slots or the output arrays. A paced connection costs a loop of up to max_buffers steps in each of two launches. */
+int cts_tcp_exchange_send_paced(cts_engine* engine, void* dev_arena, uint64_t arena_bytes, uint32_t stride,
+                                uint64_t first_slot, uint32_t capacity, const uint32_t* dev_conn_ids, uint32_t n,
+                                uint32_t max_buffers, cts_tcp_exchange_state* dev_entries,
+                                cts_tcp_sender_pace* dev_pace, uint32_t n_conns, int64_t now_ms,
+                                cts_buf_desc* dev_descs, uint32_t* dev_codes, cts_tcp_exchange_paced_tick* dev_tick,
+                                void* dev_sent_counters, void* dev_scratch, size_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -36,8 +36,8 @@
  *   - -Buffer:[lo,hi] random buffer sizes: an entry has one buffer_size
  *   - a ring that wraps: a tick writes the slots first_slot .. first_slot + total of one flat arena
  *   - handing the slots to sockets
- *   - Pull, PushPull and Duplex: cts_tcp_exchange_send (cts_tcp_exchange.h) runs all four patterns; this tick and
- *     the paced one stay -Pattern:Push
+ *   - Pull, PushPull and Duplex: cts_tcp_exchange_send and cts_tcp_exchange_send_paced (cts_tcp_exchange.h) run all
+ *     four patterns, paced or not; the two ticks of this header stay -Pattern:Push
  *
  * Conventions as cts_media_stream_servers.h: noexcept, int status, device pointers from hipMalloc, stream =
  * hipStream_t as void*. Every argument check comes before the engine is used, so a bad argument is CTS_E_INVALID with
