@@ -64,21 +64,8 @@ int env_int(const char* name, int dflt)
     return std::atoi(v);
 }
 
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = (prev == dev) || (hipSetDevice(dev) == hipSuccess);
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-inline int hip_status(hipError_t e) { return e == hipSuccess ? CTS_OK : CTS_E_HIP; }
+using cts::DeviceGuard;
+using cts::hip_status;
 
 // Pinned host memory that the device reads directly (hipHostMalloc memory is
 // mapped into the device address space).

@@ -695,26 +695,26 @@ hipError_t launch_ms_server_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t 
 // the tick's descriptors: one lane per slot of the capacity, at most the verify path's grid (the total is on the device)
 hipError_t launch_tcp_sender_descs(uint32_t stride, uint64_t first_slot, uint32_t capacity, const uint32_t* conn_ids,
                                    uint32_t n, const cts_tcp_sender_state* senders, uint32_t n_conns,
-                                   const TcpSenderScratch& scratch, const cts_tcp_sender_tick* tick,
+                                   const uint64_t* prefix, const uint64_t* before, const cts_tcp_sender_tick* tick,
                                    cts_buf_desc* descs, hipStream_t stream, const LaunchGeometry& geo)
 {
     if (n == 0 || capacity == 0) return hipSuccess;
     const uint32_t grid = grid_for((uint32_t)(((uint64_t)capacity + kBlock - 1) / kBlock), 1, geo);
     tcp_sender_descs<<<grid, kBlock, 0, stream>>>(stride, first_slot, capacity, conn_ids, n, senders, n_conns,
-                                                  scratch.prefix, scratch.before, tick, descs);
+                                                  prefix, before, tick, descs);
     return hipGetLastError();
 }
 
 // the exchange tick's descriptors: launch_tcp_sender_descs' grid
 hipError_t launch_tcp_exchange_descs(uint32_t stride, uint64_t first_slot, uint32_t capacity, const uint32_t* conn_ids,
                                      uint32_t n, const cts_tcp_exchange_state* entries, uint32_t n_conns,
-                                     const TcpExchangeScratch& scratch, const cts_tcp_exchange_tick* tick,
+                                     const uint64_t* prefix, const uint64_t* before, const cts_tcp_exchange_tick* tick,
                                      cts_buf_desc* descs, hipStream_t stream, const LaunchGeometry& geo)
 {
     if (n == 0 || capacity == 0) return hipSuccess;
     const uint32_t grid = grid_for((uint32_t)(((uint64_t)capacity + kBlock - 1) / kBlock), 1, geo);
     tcp_exchange_descs<<<grid, kBlock, 0, stream>>>(stride, first_slot, capacity, conn_ids, n, entries, n_conns,
-                                                    scratch.plain.prefix, scratch.plain.before, tick, descs);
+                                                    prefix, before, tick, descs);
     return hipGetLastError();
 }
 

@@ -198,8 +198,8 @@ hipError_t launch_ms_conn_close(const uint32_t* conn_ids, uint32_t n, uint32_t* 
                                 cts_ms_conn_result* results, uint64_t* close_counters, hipStream_t stream,
                                 const LaunchGeometry& geo);
 
-// The device-resident senders' ticks. The planning of all three (the launch_*_plan kernels, cts_tick_plan.hip) walks
-// the n listed connections in tiles of kPlanTile; the fills that follow it are in cts_fill.hip.
+// The device-resident senders' ticks. The planning of all five (launch_ms_server_plan and launch_tcp_plan,
+// cts_tick_plan.hip) walks the n listed connections in tiles of kPlanTile; the fills that follow it are in cts_fill.hip.
 //
 // MediaStream servers on the device (cts_media_stream_servers.cpp). A tick's scratch holds, in this order, the listed
 // connections' exclusive prefix of wanted slots and its grand total (n + 1 words), the tiles' sums, and a tick block
@@ -233,139 +233,130 @@ hipError_t launch_ms_server_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t 
                                  const cts_ms_server_tick* tick, int64_t qpc, int64_t qpf, cts_buf_desc* descs,
                                  uint32_t* lengths, hipStream_t stream, const LaunchGeometry& geo);
 
-// TCP senders on the device (cts_tcp_senders.cpp). The planning is the servers' in the same tiles; a tick's scratch
-// holds, in this order, the listed connections' exclusive prefix of wanted slots and its grand total (n + 1 words),
-// the tiles' sums, each listed connection's bytes_sent from before the tick moved its entry (n words), and a tick
-// block for the caller that passes none.
-struct TcpSenderScratch {
-    uint64_t* prefix;           // n + 1
-    uint64_t* sums;             // plan_tiles(n)
-    uint64_t* before;           // n
-    cts_tcp_sender_tick* tick;  // 1
-    TcpSenderScratch(void* base, uint32_t n)
+// The four TCP ticks on the device (cts_tcp_senders.cpp, cts_tcp_exchange.cpp; their shared driver is
+// cts_tcp_tick.hpp). The planning is the servers' in the same tiles; a tick's scratch holds, in this order, the listed
+// connections' exclusive prefix of wanted slots and its grand total (n + 1 words), the tiles' sums, a word per listed
+// connection from before the tick moved its entry (n words: bytes_sent of a sender, buffers_sent of an exchange
+// entry), and a tick block for the caller that passes none. The four scratches differ in that block's type alone, so
+// the same base names the same prefix, sums and before for all of them.
+template <typename Tick>
+struct TcpTickScratch {
+    uint64_t* prefix;  // n + 1
+    uint64_t* sums;    // plan_tiles(n)
+    uint64_t* before;  // n
+    Tick* tick;        // 1
+    TcpTickScratch(void* base, uint32_t n)
         : prefix(static_cast<uint64_t*>(base)), sums(prefix + (uint64_t)n + 1), before(sums + plan_tiles(n)),
-          tick(reinterpret_cast<cts_tcp_sender_tick*>(before + n))
+          tick(reinterpret_cast<Tick*>(before + n))
     {
     }
-    static size_t bytes(uint32_t n)
+    static constexpr size_t bytes(uint32_t n)
     {
-        return (size_t)((2 * (uint64_t)n + 1 + plan_tiles(n)) * sizeof(uint64_t) + sizeof(cts_tcp_sender_tick));
+        return (size_t)((2 * (uint64_t)n + 1 + ((uint64_t)n + kPlanTile - 1) / kPlanTile) * sizeof(uint64_t) +
+                        sizeof(Tick));
     }
 };
-// The planning (three launches: tile sums, ms_server_scan, apply) writes scratch.prefix and scratch.before, the codes
-// (may be null), `tick` (zeroed first) and the sent block (may be null), and moves the entries of the connections that
-// take a slot. The descriptor pass reads them and tick->buffers and writes descs[0 .. tick->buffers); the fill runs
-// over those descriptors. Both grids come from `capacity`: launch_fill's rules with the stride as the length hint.
-hipError_t launch_tcp_sender_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
-                                  cts_tcp_sender_state* senders, uint32_t n_conns, uint32_t stride, uint32_t capacity,
-                                  uint32_t* codes, cts_tcp_sender_tick* tick, uint64_t* sent_counters,
-                                  const TcpSenderScratch& scratch, hipStream_t stream);
+// cts_tcp_senders_scratch_bytes, _paced_scratch_bytes, cts_tcp_exchange_scratch_bytes and _paced_scratch_bytes are
+// part of the ABI: 2n + 1 + ceil(n / 256) words and a block of 32, 48, 48 and 64 bytes.
+static_assert(TcpTickScratch<cts_tcp_sender_tick>::bytes(0) == 40 && TcpTickScratch<cts_tcp_sender_tick>::bytes(1) == 64 &&
+                  TcpTickScratch<cts_tcp_sender_tick>::bytes(256) == 4144 &&
+                  TcpTickScratch<cts_tcp_sender_tick>::bytes(257) == 4168,
+              "cts_tcp_senders_scratch_bytes");
+static_assert(TcpTickScratch<cts_tcp_sender_paced_tick>::bytes(0) == 56 &&
+                  TcpTickScratch<cts_tcp_sender_paced_tick>::bytes(1) == 80 &&
+                  TcpTickScratch<cts_tcp_sender_paced_tick>::bytes(256) == 4160 &&
+                  TcpTickScratch<cts_tcp_sender_paced_tick>::bytes(257) == 4184,
+              "cts_tcp_senders_paced_scratch_bytes");
+static_assert(TcpTickScratch<cts_tcp_exchange_tick>::bytes(0) == 56 && TcpTickScratch<cts_tcp_exchange_tick>::bytes(1) == 80 &&
+                  TcpTickScratch<cts_tcp_exchange_tick>::bytes(256) == 4160 &&
+                  TcpTickScratch<cts_tcp_exchange_tick>::bytes(257) == 4184,
+              "cts_tcp_exchange_scratch_bytes");
+static_assert(TcpTickScratch<cts_tcp_exchange_paced_tick>::bytes(0) == 72 &&
+                  TcpTickScratch<cts_tcp_exchange_paced_tick>::bytes(1) == 96 &&
+                  TcpTickScratch<cts_tcp_exchange_paced_tick>::bytes(256) == 4176 &&
+                  TcpTickScratch<cts_tcp_exchange_paced_tick>::bytes(257) == 4200,
+              "cts_tcp_exchange_paced_scratch_bytes");
+
+// Every tick block begins with the plain tick's 32 bytes, which the fill reads, and a paced exchange block with the
+// exchange tick's 48, which the exchange descriptor pass reads.
+#if defined(__HIP__)
+#define CTS_TICK_FN __host__ __device__ inline
+#else
+#define CTS_TICK_FN inline
+#endif
+CTS_TICK_FN cts_tcp_sender_tick* plain_tick(cts_tcp_sender_tick* t) { return t; }
+CTS_TICK_FN cts_tcp_sender_tick* plain_tick(cts_tcp_sender_paced_tick* t) { return &t->tick; }
+CTS_TICK_FN cts_tcp_sender_tick* plain_tick(cts_tcp_exchange_tick* t) { return &t->tick; }
+CTS_TICK_FN cts_tcp_sender_tick* plain_tick(cts_tcp_exchange_paced_tick* t) { return &t->tick.tick; }
+CTS_TICK_FN cts_tcp_exchange_tick* exchange_tick(cts_tcp_exchange_tick* t) { return t; }
+CTS_TICK_FN cts_tcp_exchange_tick* exchange_tick(cts_tcp_exchange_paced_tick* t) { return &t->tick; }
+#undef CTS_TICK_FN
+
+// What a TCP tick's launches read of the call's arguments, in the order of the C ABI; pace and now_ms are the paced
+// ticks'.
+struct TcpTickArgs {
+    void* arena;
+    uint64_t arena_bytes;
+    uint32_t stride;
+    uint64_t first_slot;
+    uint32_t capacity;
+    const uint32_t* conn_ids;
+    uint32_t n, max_buffers, n_conns;
+    cts_buf_desc* descs;
+    uint32_t* codes;
+    void* sent_counters;
+    void* scratch;
+    size_t scratch_bytes;
+    void* stream;
+    cts_tcp_sender_pace* pace;
+    int64_t now_ms;
+};
+
+// The planning (three launches: the tick's _sums, tick_plan_scan, the tick's _apply; cts_tick_plan.hip) writes
+// scratch.prefix and scratch.before, the codes (may be null), `tick` (initialised first) and the sent block (may be
+// null), and moves the entries of the connections that take a slot; a paced tick cuts the wanted slots by the pace
+// entries at now_ms and moves those too. Instantiated for the four (tick, entry) pairs of the ABI.
+template <typename Tick, typename Entry>
+hipError_t launch_tcp_plan(const TcpTickArgs& a, Entry* entries, Tick* tick, const TcpTickScratch<Tick>& scratch,
+                           hipStream_t stream);
+// The descriptor pass reads prefix, before, the entries and the tick's buffer count and writes descs[0 ..
+// tick->buffers), the exchange tick's by the closed form of cts_tcp_exchange_math.hpp; the fill runs over those
+// descriptors. Both grids come from `capacity`: launch_fill's rules with the stride as the length hint.
 hipError_t launch_tcp_sender_descs(uint32_t stride, uint64_t first_slot, uint32_t capacity, const uint32_t* conn_ids,
                                    uint32_t n, const cts_tcp_sender_state* senders, uint32_t n_conns,
-                                   const TcpSenderScratch& scratch, const cts_tcp_sender_tick* tick,
+                                   const uint64_t* prefix, const uint64_t* before, const cts_tcp_sender_tick* tick,
                                    cts_buf_desc* descs, hipStream_t stream, const LaunchGeometry& geo);
+hipError_t launch_tcp_exchange_descs(uint32_t stride, uint64_t first_slot, uint32_t capacity, const uint32_t* conn_ids,
+                                     uint32_t n, const cts_tcp_exchange_state* entries, uint32_t n_conns,
+                                     const uint64_t* prefix, const uint64_t* before, const cts_tcp_exchange_tick* tick,
+                                     cts_buf_desc* descs, hipStream_t stream, const LaunchGeometry& geo);
 hipError_t launch_tcp_sender_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t stride, uint32_t capacity,
                                   const cts_buf_desc* descs, const cts_tcp_sender_tick* tick, hipStream_t stream,
                                   const LaunchGeometry& geo);
 
-// The paced tick (cts_tcp_senders_send_paced). Its scratch is the plain tick's with the
-// 48-byte tick block at the end, so a TcpSenderScratch over the same base names the same prefix, sums and before,
-// and the descriptor pass and the fill read the paced block's first 32 bytes as the plain tick they expect.
-struct TcpPacedScratch {
-    TcpSenderScratch plain;
-    cts_tcp_sender_paced_tick* tick;  // 1
-    TcpPacedScratch(void* base, uint32_t n)
-        : plain(base, n), tick(reinterpret_cast<cts_tcp_sender_paced_tick*>(plain.tick))
-    {
-    }
-    static size_t bytes(uint32_t n)
-    {
-        return TcpSenderScratch::bytes(n) - sizeof(cts_tcp_sender_tick) + sizeof(cts_tcp_sender_paced_tick);
-    }
-};
-// The paced planning (three launches: tile sums, the paced scan, apply): what launch_tcp_sender_plan writes, with the
-// wanted slots cut by the pace entries at now_ms, the pace entries moved, and the tick's 16-byte tail.
-hipError_t launch_tcp_paced_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
-                                 cts_tcp_sender_state* senders, cts_tcp_sender_pace* pace, uint32_t n_conns,
-                                 int64_t now_ms, uint32_t stride, uint32_t capacity, uint32_t* codes,
-                                 cts_tcp_sender_paced_tick* tick, uint64_t* sent_counters,
-                                 const TcpPacedScratch& scratch, hipStream_t stream);
-
-// The exchange tick (cts_tcp_exchange_send): the senders' scheme over 64-byte entries whose buffers go either way.
-// Its scratch is the plain tick's with `before` holding each listed connection's buffers_sent from before the move
-// and the 48-byte tick block at the end; the fill reads the block's first 32 bytes as the plain tick it expects.
-struct TcpExchangeScratch {
-    TcpSenderScratch plain;
-    cts_tcp_exchange_tick* tick;  // 1
-    TcpExchangeScratch(void* base, uint32_t n)
-        : plain(base, n), tick(reinterpret_cast<cts_tcp_exchange_tick*>(plain.tick))
-    {
-    }
-    static size_t bytes(uint32_t n)
-    {
-        return TcpSenderScratch::bytes(n) - sizeof(cts_tcp_sender_tick) + sizeof(cts_tcp_exchange_tick);
-    }
-};
-// The planning (three launches: tcp_exchange_sums, _scan, _apply) writes what launch_tcp_sender_plan writes, with
-// the tick's bytes by direction; the descriptor pass turns prefix, before and the entries' constants into descs[0 ..
-// tick->tick.buffers) by the closed form of cts_tcp_exchange_math.hpp.
-hipError_t launch_tcp_exchange_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
-                                    cts_tcp_exchange_state* entries, uint32_t n_conns, uint32_t stride,
-                                    uint32_t capacity, uint32_t* codes, cts_tcp_exchange_tick* tick,
-                                    uint64_t* sent_counters, const TcpExchangeScratch& scratch, hipStream_t stream);
-hipError_t launch_tcp_exchange_descs(uint32_t stride, uint64_t first_slot, uint32_t capacity, const uint32_t* conn_ids,
-                                     uint32_t n, const cts_tcp_exchange_state* entries, uint32_t n_conns,
-                                     const TcpExchangeScratch& scratch, const cts_tcp_exchange_tick* tick,
-                                     cts_buf_desc* descs, hipStream_t stream, const LaunchGeometry& geo);
-
-// The paced exchange tick (cts_tcp_exchange_send_paced). Its scratch is the exchange tick's with the 64-byte tick
-// block at the end: the descriptor pass reads the block's first 48 bytes as the exchange tick it expects, the fill its
-// first 32.
-struct TcpExchangePacedScratch {
-    TcpExchangeScratch exchange;
-    cts_tcp_exchange_paced_tick* tick;  // 1
-    TcpExchangePacedScratch(void* base, uint32_t n)
-        : exchange(base, n), tick(reinterpret_cast<cts_tcp_exchange_paced_tick*>(exchange.tick))
-    {
-    }
-    static size_t bytes(uint32_t n)
-    {
-        return TcpExchangeScratch::bytes(n) - sizeof(cts_tcp_exchange_tick) + sizeof(cts_tcp_exchange_paced_tick);
-    }
-};
-// The paced planning (three launches: tcp_exchange_paced_sums, _scan, _apply): what launch_tcp_exchange_plan writes,
-// with the wanted slots cut by the 2 x n_conns pace entries at now_ms, the pace entries moved, and the tick's tail.
-hipError_t launch_tcp_exchange_paced_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
-                                          cts_tcp_exchange_state* entries, cts_tcp_sender_pace* pace,
-                                          uint32_t n_conns, int64_t now_ms, uint32_t stride, uint32_t capacity,
-                                          uint32_t* codes, cts_tcp_exchange_paced_tick* tick, uint64_t* sent_counters,
-                                          const TcpExchangePacedScratch& scratch, hipStream_t stream);
-
-// What the arguments of a TCP tick must satisfy (cts_tcp_senders_send, _send_paced, cts_tcp_exchange_send,
-// _send_paced) once n != 0; dev_entries = the connections' table, need = the scratch size of that tick.
 inline bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1u)) != 0; }
-inline bool tick_args_ok(const void* dev_arena, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
-                         uint32_t capacity, const uint32_t* dev_conn_ids, uint32_t max_buffers,
-                         const void* dev_entries, uint32_t n_conns, const cts_buf_desc* dev_descs,
-                         const uint32_t* dev_codes, const void* dev_tick, const void* dev_sent_counters,
-                         const void* dev_scratch, size_t scratch_bytes, size_t need)
-{
-    if ((stride & 15u) != 0u || stride < 16u || stride > (16u << 20)) return false;
-    if (max_buffers == 0u) return false;
-    if (dev_arena == nullptr || misaligned(dev_arena, 16)) return false;
-    // (first_slot + capacity) x stride <= arena_bytes, without wrap-around: compared in slots
-    if (first_slot > arena_bytes / stride || (uint64_t)capacity > arena_bytes / stride - first_slot) return false;
-    if (dev_conn_ids == nullptr || misaligned(dev_conn_ids, 4)) return false;
-    if ((n_conns != 0 && dev_entries == nullptr) || misaligned(dev_entries, 8)) return false;
-    if (dev_descs == nullptr || misaligned(dev_descs, 8)) return false;
-    if (misaligned(dev_codes, 4) || misaligned(dev_tick, 8) || misaligned(dev_sent_counters, 8)) return false;
-    return dev_scratch != nullptr && !misaligned(dev_scratch, 8) && scratch_bytes >= need;
-}
 
 // The engine's device and launch geometry for the entry points that live outside cts_engine.cpp (cts_refview.cpp,
 // cts_connections.cpp, cts_media_stream_conns.cpp, cts_media_stream_servers.cpp, cts_tcp_senders.cpp);
 // e != nullptr. Defined in cts_engine.cpp, where cts_engine is complete.
 const LaunchGeometry& engine_geometry(const cts_engine* e, int* device);
+
+// Makes `dev` the calling thread's device for a scope and puts the previous one back; ok = the device is current.
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = false;
+    explicit DeviceGuard(int dev)
+    {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        ok = (prev == dev) || (hipSetDevice(dev) == hipSuccess);
+    }
+    ~DeviceGuard()
+    {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+inline int hip_status(hipError_t e) { return e == hipSuccess ? CTS_OK : CTS_E_HIP; }
 
 hipError_t launch_fill(uint8_t* arena, uint64_t arena_bytes, const cts_buf_desc* descs, uint32_t n,
                        uint32_t max_length_hint, hipStream_t stream, const LaunchGeometry& geo);

@@ -10,6 +10,7 @@
 #include "cts_internal.hpp"
 #include "cts_tcp_exchange.h"
 #include "cts_tcp_exchange_math.hpp"
+#include "cts_tcp_tick.hpp"
 
 static_assert(sizeof(cts_tcp_exchange_state) == 64 && alignof(cts_tcp_exchange_state) == 8,
               "cts_tcp_exchange_state: 64 bytes");
@@ -22,19 +23,18 @@ static_assert(sizeof(cts_tcp_exchange_paced_tick) == 64 && alignof(cts_tcp_excha
 
 namespace {
 
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = (prev == dev) || (hipSetDevice(dev) == hipSuccess);
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
+// the direction-1 receiver, and a paced tick's direction-1 pace entry, of connection c is c + n_conns
+bool receivers_ok(const cts::TcpTickArgs& a) { return a.n_conns <= (1u << 31); }
+
+// The descriptor pass of both ticks, the plain exchange tick's: it reads the tick block's first 48 bytes.
+auto exchange_descs(const cts::TcpTickArgs& a, const cts_tcp_exchange_state* entries)
+{
+    return [&a, entries](const auto& scratch, auto* tick, hipStream_t s, const cts::LaunchGeometry& geo) {
+        return cts::launch_tcp_exchange_descs(a.stride, a.first_slot, a.capacity, a.conn_ids, a.n, entries, a.n_conns,
+                                              scratch.prefix, scratch.before, cts::exchange_tick(tick), a.descs, s,
+                                              geo);
+    };
+}
 
 // An entry as cts_tcp_exchange_init makes it, wherever it has been moved since.
 bool well_formed(const cts_tcp_exchange_state* e)
@@ -110,7 +110,7 @@ uint64_t cts_tcp_exchange_direction_bytes(const cts_tcp_exchange_state* entry, u
     return cts::exchange_direction_total(cts::exchange_shape(entry), direction);
 }
 
-size_t cts_tcp_exchange_scratch_bytes(uint32_t n) { return cts::TcpExchangeScratch::bytes(n); }
+size_t cts_tcp_exchange_scratch_bytes(uint32_t n) { return cts::TcpTickScratch<cts_tcp_exchange_tick>::bytes(n); }
 
 int cts_tcp_exchange_send(cts_engine* e, void* dev_arena, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
                           uint32_t capacity, const uint32_t* dev_conn_ids, uint32_t n, uint32_t max_buffers,
@@ -118,37 +118,16 @@ int cts_tcp_exchange_send(cts_engine* e, void* dev_arena, uint64_t arena_bytes, 
                           uint32_t* dev_codes, cts_tcp_exchange_tick* dev_tick, void* dev_sent_counters,
                           void* dev_scratch, size_t scratch_bytes, void* stream)
 {
-    if (e == nullptr) return CTS_E_INVALID;
-    if (n == 0) return CTS_OK;
-    if (!cts::tick_args_ok(dev_arena, arena_bytes, stride, first_slot, capacity, dev_conn_ids, max_buffers,
-                           dev_entries, n_conns, dev_descs, dev_codes, dev_tick, dev_sent_counters, dev_scratch,
-                           scratch_bytes, cts::TcpExchangeScratch::bytes(n)))
-        return CTS_E_INVALID;
-    if (n_conns > (1u << 31)) return CTS_E_INVALID;  // the direction-1 receiver of connection c is c + n_conns
-    int device = 0;
-    const cts::LaunchGeometry& geo = cts::engine_geometry(e, &device);
-    DeviceGuard g(device);
-    if (!g.ok) return CTS_E_HIP;
-    const cts::TcpExchangeScratch scratch(dev_scratch, n);
-    // the descriptor pass and the fill read the tick's buffer count: a caller that wants no tick block gets the
-    // scratch's
-    cts_tcp_exchange_tick* const tick = dev_tick != nullptr ? dev_tick : scratch.tick;
-    hipStream_t const s = static_cast<hipStream_t>(stream);
-    hipError_t rc = cts::launch_tcp_exchange_plan(dev_conn_ids, n, max_buffers, dev_entries, n_conns, stride,
-                                                  capacity, dev_codes, tick,
-                                                  static_cast<uint64_t*>(dev_sent_counters), scratch, s);
-    if (rc != hipSuccess) return CTS_E_HIP;
-    rc = cts::launch_tcp_exchange_descs(stride, first_slot, capacity, dev_conn_ids, n, dev_entries, n_conns, scratch,
-                                        tick, dev_descs, s, geo);
-    if (rc != hipSuccess) return CTS_E_HIP;
-    // the fill is the senders': it reads the block's first 32 bytes
-    return cts::launch_tcp_sender_fill(static_cast<uint8_t*>(dev_arena), arena_bytes, stride, capacity, dev_descs,
-                                       &tick->tick, s, geo) == hipSuccess
-               ? CTS_OK
-               : CTS_E_HIP;
+    const cts::TcpTickArgs a{dev_arena, arena_bytes, stride, first_slot, capacity, dev_conn_ids, n, max_buffers, n_conns,
+                             dev_descs, dev_codes, dev_sent_counters, dev_scratch, scratch_bytes, stream, nullptr, 0};
+    return cts::tcp_tick_send(e, a, dev_entries, dev_tick, [&] { return receivers_ok(a); },
+                              exchange_descs(a, dev_entries));
 }
 
-size_t cts_tcp_exchange_paced_scratch_bytes(uint32_t n) { return cts::TcpExchangePacedScratch::bytes(n); }
+size_t cts_tcp_exchange_paced_scratch_bytes(uint32_t n)
+{
+    return cts::TcpTickScratch<cts_tcp_exchange_paced_tick>::bytes(n);
+}
 
 int cts_tcp_exchange_send_paced(cts_engine* e, void* dev_arena, uint64_t arena_bytes, uint32_t stride,
                                 uint64_t first_slot, uint32_t capacity, const uint32_t* dev_conn_ids, uint32_t n,
@@ -157,34 +136,10 @@ int cts_tcp_exchange_send_paced(cts_engine* e, void* dev_arena, uint64_t arena_b
                                 cts_buf_desc* dev_descs, uint32_t* dev_codes, cts_tcp_exchange_paced_tick* dev_tick,
                                 void* dev_sent_counters, void* dev_scratch, size_t scratch_bytes, void* stream)
 {
-    if (e == nullptr) return CTS_E_INVALID;
-    if (n == 0) return CTS_OK;
-    if (!cts::tick_args_ok(dev_arena, arena_bytes, stride, first_slot, capacity, dev_conn_ids, max_buffers,
-                           dev_entries, n_conns, dev_descs, dev_codes, dev_tick, dev_sent_counters, dev_scratch,
-                           scratch_bytes, cts::TcpExchangePacedScratch::bytes(n)))
-        return CTS_E_INVALID;
-    if (n_conns > (1u << 31)) return CTS_E_INVALID;  // receiver and pace entry c + n_conns
-    if (now_ms < 0) return CTS_E_INVALID;
-    if ((n_conns != 0 && dev_pace == nullptr) || cts::misaligned(dev_pace, 8)) return CTS_E_INVALID;
-    int device = 0;
-    const cts::LaunchGeometry& geo = cts::engine_geometry(e, &device);
-    DeviceGuard g(device);
-    if (!g.ok) return CTS_E_HIP;
-    const cts::TcpExchangePacedScratch scratch(dev_scratch, n);
-    cts_tcp_exchange_paced_tick* const tick = dev_tick != nullptr ? dev_tick : scratch.tick;
-    hipStream_t const s = static_cast<hipStream_t>(stream);
-    hipError_t rc = cts::launch_tcp_exchange_paced_plan(dev_conn_ids, n, max_buffers, dev_entries, dev_pace, n_conns,
-                                                        now_ms, stride, capacity, dev_codes, tick,
-                                                        static_cast<uint64_t*>(dev_sent_counters), scratch, s);
-    if (rc != hipSuccess) return CTS_E_HIP;
-    // the descriptor pass and the fill are the plain tick's: they read the block's first 48 and 32 bytes
-    rc = cts::launch_tcp_exchange_descs(stride, first_slot, capacity, dev_conn_ids, n, dev_entries, n_conns,
-                                        scratch.exchange, &tick->tick, dev_descs, s, geo);
-    if (rc != hipSuccess) return CTS_E_HIP;
-    return cts::launch_tcp_sender_fill(static_cast<uint8_t*>(dev_arena), arena_bytes, stride, capacity, dev_descs,
-                                       &tick->tick.tick, s, geo) == hipSuccess
-               ? CTS_OK
-               : CTS_E_HIP;
+    const cts::TcpTickArgs a{dev_arena, arena_bytes, stride, first_slot, capacity, dev_conn_ids, n, max_buffers, n_conns,
+                             dev_descs, dev_codes, dev_sent_counters, dev_scratch, scratch_bytes, stream, dev_pace, now_ms};
+    return cts::tcp_tick_send(e, a, dev_entries, dev_tick, [&] { return receivers_ok(a) && cts::pace_args_ok(a); },
+                              exchange_descs(a, dev_entries));
 }
 
 }  // extern "C"

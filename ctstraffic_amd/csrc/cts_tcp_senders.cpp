@@ -8,6 +8,7 @@
 
 #include "cts_internal.hpp"
 #include "cts_tcp_senders.h"
+#include "cts_tcp_tick.hpp"
 
 static_assert(sizeof(cts_tcp_sender_state) == 32 && alignof(cts_tcp_sender_state) == 8, "cts_tcp_sender_state: 32 bytes");
 static_assert(sizeof(cts_tcp_sender_tick) == 32 && alignof(cts_tcp_sender_tick) == 8, "cts_tcp_sender_tick: 32 bytes");
@@ -18,24 +19,14 @@ static_assert(sizeof(cts_counters_sent) == 6 * sizeof(uint64_t), "a sent block's
 
 namespace {
 
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = (prev == dev) || (hipSetDevice(dev) == hipSuccess);
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-inline int hip_status(hipError_t e) { return e == hipSuccess ? CTS_OK : CTS_E_HIP; }
-
-using cts::misaligned;
-using cts::tick_args_ok;
+// The descriptor pass of both ticks, the plain tick's: it reads the tick block's first 32 bytes.
+auto sender_descs(const cts::TcpTickArgs& a, const cts_tcp_sender_state* senders)
+{
+    return [&a, senders](const auto& scratch, auto* tick, hipStream_t s, const cts::LaunchGeometry& geo) {
+        return cts::launch_tcp_sender_descs(a.stride, a.first_slot, a.capacity, a.conn_ids, a.n, senders, a.n_conns,
+                                            scratch.prefix, scratch.before, cts::plain_tick(tick), a.descs, s, geo);
+    };
+}
 
 inline cts_counters_sent sent_of(const cts_counters_ex& x)
 {
@@ -55,7 +46,7 @@ int cts_tcp_sender_init(uint64_t transfer_bytes, uint32_t buffer_size, cts_tcp_s
     return CTS_OK;
 }
 
-size_t cts_tcp_senders_scratch_bytes(uint32_t n) { return cts::TcpSenderScratch::bytes(n); }
+size_t cts_tcp_senders_scratch_bytes(uint32_t n) { return cts::TcpTickScratch<cts_tcp_sender_tick>::bytes(n); }
 
 int cts_tcp_senders_send(cts_engine* e, void* dev_arena, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
                          uint32_t capacity, const uint32_t* dev_conn_ids, uint32_t n, uint32_t max_buffers,
@@ -63,29 +54,9 @@ int cts_tcp_senders_send(cts_engine* e, void* dev_arena, uint64_t arena_bytes, u
                          uint32_t* dev_codes, cts_tcp_sender_tick* dev_tick, void* dev_sent_counters,
                          void* dev_scratch, size_t scratch_bytes, void* stream)
 {
-    if (e == nullptr) return CTS_E_INVALID;
-    if (n == 0) return CTS_OK;
-    if (!tick_args_ok(dev_arena, arena_bytes, stride, first_slot, capacity, dev_conn_ids, max_buffers, dev_senders,
-                      n_conns, dev_descs, dev_codes, dev_tick, dev_sent_counters, dev_scratch, scratch_bytes,
-                      cts::TcpSenderScratch::bytes(n)))
-        return CTS_E_INVALID;
-    int device = 0;
-    const cts::LaunchGeometry& geo = cts::engine_geometry(e, &device);
-    DeviceGuard g(device);
-    if (!g.ok) return CTS_E_HIP;
-    const cts::TcpSenderScratch scratch(dev_scratch, n);
-    // the descriptor pass and the fill read the tick's buffer count: a caller that wants no tick block gets the
-    // scratch's
-    cts_tcp_sender_tick* const tick = dev_tick != nullptr ? dev_tick : scratch.tick;
-    hipStream_t const s = static_cast<hipStream_t>(stream);
-    hipError_t rc = cts::launch_tcp_sender_plan(dev_conn_ids, n, max_buffers, dev_senders, n_conns, stride, capacity,
-                                                dev_codes, tick, static_cast<uint64_t*>(dev_sent_counters), scratch, s);
-    if (rc != hipSuccess) return CTS_E_HIP;
-    rc = cts::launch_tcp_sender_descs(stride, first_slot, capacity, dev_conn_ids, n, dev_senders, n_conns, scratch,
-                                      tick, dev_descs, s, geo);
-    if (rc != hipSuccess) return CTS_E_HIP;
-    return hip_status(cts::launch_tcp_sender_fill(static_cast<uint8_t*>(dev_arena), arena_bytes, stride, capacity,
-                                                  dev_descs, tick, s, geo));
+    const cts::TcpTickArgs a{dev_arena, arena_bytes, stride, first_slot, capacity, dev_conn_ids, n, max_buffers, n_conns,
+                             dev_descs, dev_codes, dev_sent_counters, dev_scratch, scratch_bytes, stream, nullptr, 0};
+    return cts::tcp_tick_send(e, a, dev_senders, dev_tick, [] { return true; }, sender_descs(a, dev_senders));
 }
 
 int cts_tcp_sender_pace_init(uint64_t bytes_per_second, uint32_t period_ms, uint32_t burst_count,
@@ -105,7 +76,10 @@ int cts_tcp_sender_pace_init(uint64_t bytes_per_second, uint32_t period_ms, uint
     return CTS_OK;
 }
 
-size_t cts_tcp_senders_paced_scratch_bytes(uint32_t n) { return cts::TcpPacedScratch::bytes(n); }
+size_t cts_tcp_senders_paced_scratch_bytes(uint32_t n)
+{
+    return cts::TcpTickScratch<cts_tcp_sender_paced_tick>::bytes(n);
+}
 
 int cts_tcp_senders_send_paced(cts_engine* e, void* dev_arena, uint64_t arena_bytes, uint32_t stride,
                                uint64_t first_slot, uint32_t capacity, const uint32_t* dev_conn_ids, uint32_t n,
@@ -114,31 +88,10 @@ int cts_tcp_senders_send_paced(cts_engine* e, void* dev_arena, uint64_t arena_by
                                cts_tcp_sender_paced_tick* dev_tick, void* dev_sent_counters, void* dev_scratch,
                                size_t scratch_bytes, void* stream)
 {
-    if (e == nullptr) return CTS_E_INVALID;
-    if (n == 0) return CTS_OK;
-    if (!tick_args_ok(dev_arena, arena_bytes, stride, first_slot, capacity, dev_conn_ids, max_buffers, dev_senders,
-                      n_conns, dev_descs, dev_codes, dev_tick, dev_sent_counters, dev_scratch, scratch_bytes,
-                      cts::TcpPacedScratch::bytes(n)))
-        return CTS_E_INVALID;
-    if (now_ms < 0) return CTS_E_INVALID;
-    if ((n_conns != 0 && dev_pace == nullptr) || misaligned(dev_pace, 8)) return CTS_E_INVALID;
-    int device = 0;
-    const cts::LaunchGeometry& geo = cts::engine_geometry(e, &device);
-    DeviceGuard g(device);
-    if (!g.ok) return CTS_E_HIP;
-    const cts::TcpPacedScratch scratch(dev_scratch, n);
-    cts_tcp_sender_paced_tick* const tick = dev_tick != nullptr ? dev_tick : scratch.tick;
-    hipStream_t const s = static_cast<hipStream_t>(stream);
-    hipError_t rc = cts::launch_tcp_paced_plan(dev_conn_ids, n, max_buffers, dev_senders, dev_pace, n_conns, now_ms,
-                                               stride, capacity, dev_codes, tick,
-                                               static_cast<uint64_t*>(dev_sent_counters), scratch, s);
-    if (rc != hipSuccess) return CTS_E_HIP;
-    // the descriptor pass and the fill are the plain tick's: they read the block's first 32 bytes
-    rc = cts::launch_tcp_sender_descs(stride, first_slot, capacity, dev_conn_ids, n, dev_senders, n_conns,
-                                      scratch.plain, &tick->tick, dev_descs, s, geo);
-    if (rc != hipSuccess) return CTS_E_HIP;
-    return hip_status(cts::launch_tcp_sender_fill(static_cast<uint8_t*>(dev_arena), arena_bytes, stride, capacity,
-                                                  dev_descs, &tick->tick, s, geo));
+    const cts::TcpTickArgs a{dev_arena, arena_bytes, stride, first_slot, capacity, dev_conn_ids, n, max_buffers, n_conns,
+                             dev_descs, dev_codes, dev_sent_counters, dev_scratch, scratch_bytes, stream, dev_pace, now_ms};
+    return cts::tcp_tick_send(e, a, dev_senders, dev_tick, [&] { return cts::pace_args_ok(a); },
+                              sender_descs(a, dev_senders));
 }
 
 // The reads are the *_ex reads: the same fold (and the same ncclAllReduce of count 6) over a block of the same

@@ -3,25 +3,29 @@
 // cts_tcp_senders_send, cts_tcp_senders_send_paced, cts_tcp_exchange_send, cts_tcp_exchange_send_paced): listed
 // connection i wants w_i slots (0 when it sends nothing whatever the room); p_i, the exclusive 64-bit prefix of the
 // wants in listed order, is its first slot, and the room left at p_i decides what it takes. Three plain launches in
-// tiles of kPlanTile listed connections (no workgroup ever waits for another):
-//   *_sums    each tile's sum of wants                              -> sums[tile]
-//   *_scan    one workgroup: exclusive scan of the tile sums in place in passes of kBlock tiles, prefix[n] = the grand
-//             total, the tick block initialised
-//   *_apply   p_i = sums[tile] + the tile's own scan -> prefix[i]; the code, the entries' updates, the tick block and
-//             the counter block
-//   ms_server_sums / _scan / _apply     the MediaStream servers: a connection sends its whole frame or nothing
-//   tcp_sender_sums / _apply            the TCP senders (with ms_server_scan: both tick blocks are eight dwords)
-//   tcp_paced_sums / _scan / _apply     the paced TCP senders: the wants cut to what CreateNewTask's send branch
-//                                       (ctsIOPattern.cpp:593-674) lets out at now_ms, from a pace entry per connection
-//   tcp_exchange_sums / _scan / _apply  the exchange tick (cts_tcp_exchange_send): Push, Pull, PushPull and Duplex
-//                                       connections, the wants counted in buffers of a fixed sequence
-//   tcp_exchange_paced_sums / _scan / _apply  the paced exchange tick (cts_tcp_exchange_send_paced): those wants cut
-//                                       by the pace entries of the two sides, one walk over directions and quanta
-// Each step of the scheme is written once here (the tile scan, the tile-sum tail, the scan's passes, the TCP limit, the
-// TCP entry move, the apply tail). What writes the ring from prefix[] is in cts_fill.hip, beside the loops it shares
-// with the other fills.
-// Scratch (MsServerScratch, TcpSenderScratch, TcpPacedScratch of cts_internal.hpp): u64 prefix[n + 1], u64 sums[tiles],
-// for the TCP senders u64 before[n], and a tick.
+// tiles of kPlanTile listed connections (no workgroup ever waits for another), issued by launch_plan:
+//   *_sums          each tile's sum of wants                              -> sums[tile]
+//   tick_plan_scan  one workgroup, one kernel for all five ticks: exclusive scan of the tile sums in place in passes
+//                   of kBlock tiles, prefix[n] = the grand total, the tick block initialised
+//   *_apply         p_i = sums[tile] + the tile's own scan -> prefix[i]; the code, the entries' updates, the tick block
+//                   and the counter block
+// The steps every planner shares come first (the tile scan, the tile-sum tail, the scan's passes, the apply tails, the
+// scan kernel, the three launches). Then
+//   ms_server_sums / _apply   the MediaStream servers, with a body of their own: a connection sends its whole frame or
+//                             nothing, and the tick moves another kind of entry
+//   tcp_tick_sums / _apply    the frame of the four TCP ticks, written once over a lane type: the index, the scan, the
+//                             clamp to the capacity, the ladder of codes, the stores, the wave sums, the sent block and
+//                             the tick block with its tails
+//   SenderLane, PacedSenderLane, ExchangeLane, PacedExchangeLane
+//                             what differs between the four: the entry and tick types, a lane's registers, want() (the
+//                             slots a connection asks for), move() (the entry's update and the bytes by direction),
+//                             what goes to before[], and for the paced two the pace registers' keep / reload / rerun
+//                             and their pending task. The pace machine (PaceRegs: CreateNewTask's send branch and the
+//                             walk that repeats it) is written once for both.
+//   tcp_sender_ / tcp_paced_ / tcp_exchange_ / tcp_exchange_paced_ sums and apply: the frame over one lane type each
+// What writes the ring from prefix[] is in cts_fill.hip, beside the loops it shares with the other fills.
+// Scratch (MsServerScratch, TcpTickScratch<Tick> of cts_internal.hpp): u64 prefix[n + 1], u64 sums[tiles], for the TCP
+// ticks u64 before[n], and a tick.
 #include <hip/hip_runtime.h>
 
 #include "cts_chunks.hpp"
@@ -33,10 +37,12 @@ namespace cts {
 static_assert(sizeof(cts_tcp_exchange_tick) == 48 && offsetof(cts_tcp_exchange_tick, bytes_dir) == 32,
               "cts_tcp_exchange_tick: a plain tick and 16 bytes");
 static_assert(kPlanTile == (uint32_t)kBlock, "one listed connection per thread of a tile");
-static_assert(sizeof(cts_tcp_sender_tick) == sizeof(cts_ms_server_tick), "ms_server_scan zeroes either tick block");
 static_assert(sizeof(cts_tcp_sender_pace) == 64 && alignof(cts_tcp_sender_pace) == 8, "cts_tcp_sender_pace: 64 bytes");
 static_assert(sizeof(cts_tcp_sender_paced_tick) == 48 && offsetof(cts_tcp_sender_paced_tick, next_due_ms) == 32,
               "cts_tcp_sender_paced_tick: a plain tick and 16 bytes");
+static_assert(sizeof(cts_tcp_exchange_paced_tick) == 64 && offsetof(cts_tcp_exchange_paced_tick, next_due_ms) == 48 &&
+                  offsetof(cts_tcp_exchange_paced_tick, connections_waiting) == 56,
+              "cts_tcp_exchange_paced_tick: an exchange tick and the paced tick's 16-byte tail");
 
 namespace {
 
@@ -81,7 +87,7 @@ __device__ __forceinline__ void tile_sum_store(uint64_t want, uint64_t* wsum, ui
     }
 }
 
-// The body of a *_scan kernel (one workgroup): sums[] becomes its own exclusive scan, kBlock tiles a pass with the
+// The body of the scan kernel (one workgroup): sums[] becomes its own exclusive scan, kBlock tiles a pass with the
 // passes' carry; the grand total is returned to every thread.
 __device__ __forceinline__ uint64_t tile_sums_scan(uint64_t* __restrict__ sums, uint64_t tiles, uint64_t* wsum)
 {
@@ -129,6 +135,16 @@ __device__ __forceinline__ void apply_flush(const uint32_t (&words)[WORDS], uint
 // threads at, at + 1 add the waves' dir[][0 .. 1] to tick_dir. Both arrays are written before apply_flush's barrier.
 constexpr int64_t kNoDue = INT64_MAX;
 
+__device__ __forceinline__ int64_t wave_min64(int64_t v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const int64_t u = (int64_t)__shfl_xor((long long)v, off, 64);
+        v = u < v ? u : v;
+    }
+    return v;
+}
+
 __device__ __forceinline__ void apply_flush_due(const int64_t* due, int64_t* tick_due, uint32_t at)
 {
     if (threadIdx.x == at) {
@@ -148,6 +164,42 @@ __device__ __forceinline__ void apply_flush_dir(const uint64_t (*dir)[2], uint64
         for (int w = 0; w < kBlock / 64; ++w) s += dir[w][d];
         if (s) atomicAdd((unsigned long long*)&tick_dir[d], (unsigned long long)s);
     }
+}
+
+// tick_plan_scan's max_at for a tick block without a word that starts at INT64_MAX (no thread index reaches it)
+constexpr uint32_t kNoMaxWord = 0x7FFFFFFFu;
+
+}  // namespace
+
+// One workgroup. tick is `dwords` 32-bit words, zeroed, but for the 64-bit word at dword max_at, which starts at
+// INT64_MAX (a paced tick's next_due_ms; kNoMaxWord = the block has none).
+__global__ void __launch_bounds__(kBlock)
+    tick_plan_scan(uint64_t* __restrict__ sums, uint64_t tiles, uint64_t* __restrict__ prefix_total,
+                   uint32_t* __restrict__ tick, uint32_t dwords, uint32_t max_at)
+{
+    __shared__ uint64_t wsum[kBlock / 64];
+    const uint64_t total = tile_sums_scan(sums, tiles, wsum);
+    if (threadIdx.x == 0u) *prefix_total = total;
+    if (threadIdx.x < dwords)
+        tick[threadIdx.x] = threadIdx.x == max_at ? 0xFFFFFFFFu : threadIdx.x == max_at + 1u ? 0x7FFFFFFFu : 0u;
+}
+
+namespace {
+
+// A tick's planning: three launches, the middle one a single workgroup. sums(tiles) and apply(tiles) launch the tick's
+// own two kernels on that many workgroups.
+template <typename Tick, typename Sums, typename Apply>
+hipError_t launch_plan(uint32_t n, uint64_t* tile_sums, uint64_t* prefix, Tick* tick, uint32_t max_at,
+                       hipStream_t stream, Sums sums, Apply apply)
+{
+    static_assert(sizeof(Tick) % 4u == 0u && sizeof(Tick) / 4u <= (size_t)kBlock, "a thread per dword of the block");
+    if (n == 0) return hipSuccess;
+    const uint64_t tiles = plan_tiles(n);
+    sums((uint32_t)tiles);
+    tick_plan_scan<<<1, kBlock, 0, stream>>>(tile_sums, tiles, prefix + n, reinterpret_cast<uint32_t*>(tick),
+                                             (uint32_t)(sizeof(Tick) / 4u), max_at);
+    apply((uint32_t)tiles);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -182,17 +234,6 @@ __global__ void __launch_bounds__(kBlock)
     uint32_t code;
     const uint64_t want = i < n ? ms_server_want(servers, ids[i], n_conns, stride, code) : 0u;
     tile_sum_store(want, wsum, sums);
-}
-
-// One workgroup. tick is 8 dwords (cts_ms_server_tick, cts_tcp_sender_tick).
-__global__ void __launch_bounds__(kBlock)
-    ms_server_scan(uint64_t* __restrict__ sums, uint64_t tiles, uint64_t* __restrict__ prefix_total,
-                   uint32_t* __restrict__ tick)
-{
-    __shared__ uint64_t wsum[kBlock / 64];
-    const uint64_t total = tile_sums_scan(sums, tiles, wsum);
-    if (threadIdx.x == 0u) *prefix_total = total;
-    if (threadIdx.x < sizeof(cts_ms_server_tick) / 4u) tick[threadIdx.x] = 0u;
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -253,63 +294,216 @@ __global__ void __launch_bounds__(kBlock)
     apply_flush(words, bytes, red, wsum, ctr, udp, [&](uint32_t k) { return &tick->datagrams + k; }, &tick->bytes);
 }
 
-// cts_media_stream_servers_send's planning: three launches, the middle one a single workgroup
+// cts_media_stream_servers_send's planning
 hipError_t launch_ms_server_plan(const uint32_t* conn_ids, uint32_t n, cts_ms_server_state* servers, uint32_t n_conns,
                                  uint32_t stride, uint32_t capacity, uint32_t* codes, cts_ms_server_tick* tick,
                                  uint64_t* udp_counters, const MsServerScratch& scratch, hipStream_t stream)
 {
-    if (n == 0) return hipSuccess;
-    const uint64_t tiles = plan_tiles(n);
-    ms_server_sums<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, servers, n_conns, stride, scratch.sums);
-    ms_server_scan<<<1, kBlock, 0, stream>>>(scratch.sums, tiles, scratch.prefix + n,
-                                             reinterpret_cast<uint32_t*>(tick));
-    ms_server_apply<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, servers, n_conns, stride, capacity,
-                                                            scratch.sums, scratch.prefix, codes, tick, udp_counters);
-    return hipGetLastError();
+    return launch_plan(
+        n, scratch.sums, scratch.prefix, tick, kNoMaxWord, stream,
+        [&](uint32_t tiles) {
+            ms_server_sums<<<tiles, kBlock, 0, stream>>>(conn_ids, n, servers, n_conns, stride, scratch.sums);
+        },
+        [&](uint32_t tiles) {
+            ms_server_apply<<<tiles, kBlock, 0, stream>>>(conn_ids, n, servers, n_conns, stride, capacity,
+                                                          scratch.sums, scratch.prefix, codes, tick, udp_counters);
+        });
 }
 
 // ---------------------------------------------------------------------------------------------
-// TCP senders (cts_tcp_senders_send): listed connection i wants w_i = min(max_buffers, ceil(R / B)) slots and takes
-// t_i = min(w_i, capacity - min(p_i, capacity)) of them. apply also leaves every listed connection's bytes_sent from
-// before the move in the scratch; tcp_sender_descs and the fill (cts_fill.hip) read prefix, before and the tick.
+// The frame of the four TCP ticks. Listed connection i wants w_i slots and takes t_i = min(w_i, capacity - min(p_i,
+// capacity)) of them. apply also leaves a word per listed connection from before the move in the scratch's before[];
+// the descriptor passes and the fill (cts_fill.hip) read prefix, before and the tick.
+//
+// A lane type holds the tick's uniform arguments and one listed connection's registers, and has
+//   Entry, Tick, kPaced, kTwoWay
+//   want(c, code)      the slots connection c wants and its code (CTS_TCP_SENDER_SENT, or what it is when it sends
+//                      nothing whatever the room); loads the lane's registers
+//   move(c, t, bytes)  connection c takes t > 0 slots: its entry's update, the bytes sent by direction (a one-way
+//                      tick leaves bytes[1] alone); true = the connection has ended. The only step that knows how many
+//                      slots a connection takes is the one that moves its entry.
+//   before()           the word for before[i]
+//   kPaced lanes: `paced` (the pace registers hold this connection's entries and want() has moved them), keep(c)
+//   (store them), reload(c) (load the stored entries again), rerun(t) (the walk of t steps), due_of(pending, due)
+//   (whether a task is pending, and when it is due)
+//   kTwoWay lanes: dir_of(tick), the tick block's bytes_dir
+// plain_tick(tick) of cts_internal.hpp is the 32-byte block every tick begins with.
 
 namespace {
 
-// The slots listed connection c wants whatever the time, its code when it sends nothing whatever the room or the time,
-// and R (bytes left) and B (buffer size) of a running connection.
-__device__ __forceinline__ uint32_t tcp_sender_limit(const cts_tcp_sender_state* __restrict__ senders, uint32_t c,
-                                                     uint32_t n_conns, uint32_t stride, uint32_t max_buffers,
-                                                     uint32_t& code, uint64_t& R, uint32_t& B)
+template <typename Lane>
+__device__ __forceinline__ void tcp_tick_sums(Lane lane, const uint32_t* __restrict__ ids, uint32_t n,
+                                              uint64_t* __restrict__ sums)
 {
-    code = CTS_TCP_SENDER_SKIPPED;
-    R = 0u;
-    B = 0u;
-    if (c >= n_conns) return 0u;
-    B = senders[c].buffer_size;
-    if (B == 0u || B > stride) return 0u;
-    code = CTS_TCP_SENDER_ENDED;
-    const uint64_t sent = senders[c].bytes_sent, transfer = senders[c].transfer_bytes;
-    if (senders[c].finished != 0u || sent >= transfer) return 0u;
-    code = CTS_TCP_SENDER_SENT;
-    R = transfer - sent;
-    const uint64_t k = R / B + (R % B != 0u ? 1u : 0u);
-    return k < (uint64_t)max_buffers ? (uint32_t)k : max_buffers;
+    __shared__ uint64_t wsum[kBlock / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
+    uint64_t want = 0;
+    if (i < n) {
+        uint32_t code;
+        want = lane.want(ids[i], code);
+    }
+    tile_sum_store(want, wsum, sums);
 }
 
-// Entry e takes t > 0 slots of B bytes with R bytes left: the bytes it sends; was = its bytes_sent before, ended =
-// the transfer is complete. The only step that knows how many slots a connection takes is the one that moves its entry.
-__device__ __forceinline__ uint64_t tcp_sender_move(cts_tcp_sender_state* e, uint64_t t, uint64_t R, uint32_t B,
-                                                    uint64_t& was, bool& ended)
+template <typename Lane>
+__device__ __forceinline__ void tcp_tick_apply(Lane lane, const uint32_t* __restrict__ ids, uint32_t n,
+                                               uint32_t capacity, const uint64_t* __restrict__ sums,
+                                               uint64_t* __restrict__ prefix, uint64_t* __restrict__ before,
+                                               uint32_t* __restrict__ codes, typename Lane::Tick* __restrict__ tick,
+                                               uint64_t* __restrict__ sent_block)
 {
-    was = e->bytes_sent;
-    const uint64_t full = t * B;  // t <= capacity < 2^32
-    const uint64_t bytes = full < R ? full : R;
-    e->bytes_sent = was + bytes;
-    e->buffers_sent += t;
-    ended = bytes == R;
-    if (ended) e->finished = 1u;
-    return bytes;
+    // buffers, connections_sent, _finished, _no_room, _skipped; then a paced tail's connections_waiting, _pending
+    constexpr int WORDS = Lane::kPaced ? 7 : 5;
+    // apply_flush keeps threads 0 .. WORDS busy; the tails' threads follow: bytes_dir's two, then next_due_ms's one
+    constexpr uint32_t kDirAt = 8u, kDueAt = Lane::kTwoWay ? kDirAt + 2u : kDirAt;
+    static_assert(WORDS < (int)kDirAt, "the tails' threads lie past apply_flush's");
+    __shared__ uint64_t wsum[kBlock / 64];
+    __shared__ uint64_t ctr[kBlock / 64][kCounterCount];
+    __shared__ uint32_t red[kBlock / 64][WORDS];
+    __shared__ uint64_t dir[kBlock / 64][2];  // kTwoWay
+    __shared__ int64_t due[kBlock / 64];      // kPaced
+    zero_counters<kBlock / 64>(ctr);
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
+    uint32_t code = CTS_TCP_SENDER_SENT, c = 0u;
+    uint64_t want = 0;
+    if (i < n) {
+        c = ids[i];
+        want = lane.want(c, code);
+    }
+    uint64_t total;
+    const uint64_t p = sums[blockIdx.x] + tile_scan_exclusive(want, wsum, total);
+    uint64_t bytes_by[2] = {0u, 0u};
+    int64_t my_due = kNoDue;
+    uint32_t buffers = 0, sent = 0, finished = 0, no_room = 0, skipped = 0, waiting = 0, pending = 0;
+    if (i < n) {
+        prefix[i] = p;
+        const uint64_t pc = p < (uint64_t)capacity ? p : (uint64_t)capacity;
+        const uint64_t t = want < (uint64_t)capacity - pc ? want : (uint64_t)capacity - pc;
+        if (code != CTS_TCP_SENDER_SENT) {
+            skipped = 1u;
+        } else if (Lane::kPaced && want == 0u) {
+            // pacing lets nothing out: the connection's entry stays, a pace entry may hold a new pending task
+            waiting = 1u;
+            code = CTS_TCP_SENDER_WAITING;
+            if constexpr (Lane::kPaced) lane.keep(c);
+        } else if (t == 0u) {
+            no_room = 1u;
+            code = CTS_TCP_SENDER_NO_ROOM;
+            if constexpr (Lane::kPaced) {
+                if (lane.paced) lane.reload(c);  // every entry stays: what counts below is what is stored
+            }
+        } else {
+            if constexpr (Lane::kPaced) {
+                if (lane.paced) {
+                    if (t < want) {  // cut by the capacity: the machine moves t steps from the stored entries
+                        lane.reload(c);
+                        lane.rerun((uint32_t)t);
+                    }
+                    lane.keep(c);
+                }
+            }
+            buffers = (uint32_t)t;
+            sent = 1u;
+            if (lane.move(c, t, bytes_by)) {
+                finished = 1u;
+                code = CTS_TCP_SENDER_FINISHED;
+            }
+        }
+        if constexpr (Lane::kPaced) {
+            if (skipped == 0u) lane.due_of(pending, my_due);
+        }
+        before[i] = lane.before();
+        if (codes != nullptr) codes[i] = code;
+    }
+    bytes_by[0] = wave_sum64(bytes_by[0]);
+    uint64_t bytes = bytes_by[0];
+    if constexpr (Lane::kTwoWay) {
+        bytes_by[1] = wave_sum64(bytes_by[1]);
+        bytes += bytes_by[1];
+    }
+    uint32_t words[WORDS] = {wave_sum(buffers), wave_sum(sent), wave_sum(finished), wave_sum(no_room),
+                             wave_sum(skipped)};
+    if constexpr (Lane::kPaced) {
+        words[5] = wave_sum(waiting);
+        words[6] = wave_sum(pending);
+        my_due = wave_min64(my_due);
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        uint64_t* const own = ctr[threadIdx.x >> 6];
+        own[0] = bytes;     // cts_counters_sent.bytes_sent (TcpStatusDetails.m_bytesSent of whichever side sent,
+                            // ctsIOPattern.cpp:510)
+        own[1] = words[0];  // .buffers_sent
+        own[2] = words[2];  // .connections_finished
+        if constexpr (Lane::kTwoWay) {
+            dir[threadIdx.x >> 6][0] = bytes_by[0];
+            dir[threadIdx.x >> 6][1] = bytes_by[1];
+        }
+        if constexpr (Lane::kPaced) due[threadIdx.x >> 6] = my_due;
+    }
+    cts_tcp_sender_tick* const plain = plain_tick(tick);
+    apply_flush(
+        words, bytes, red, wsum, ctr, sent_block,
+        [&](uint32_t k) {
+            if constexpr (Lane::kPaced) return k < 5u ? &plain->buffers + k : &tick->connections_waiting + (k - 5u);
+            else return &plain->buffers + k;
+        },
+        &plain->bytes);
+    if constexpr (Lane::kTwoWay) apply_flush_dir(dir, Lane::dir_of(tick), kDirAt);
+    if constexpr (Lane::kPaced) apply_flush_due(due, &tick->next_due_ms, kDueAt);
 }
+
+// A _sums kernel calls want() alone, which stores nothing: it hands its const table to a lane as the pointer move()
+// needs.
+template <typename T>
+__device__ __forceinline__ T* lane_table(const T* table)
+{
+    return const_cast<T*>(table);
+}
+
+// ---------------------------------------------------------------------------------------------
+// TCP senders (cts_tcp_senders_send): listed connection i wants w_i = min(max_buffers, ceil(R / B)) slots; before[i] is
+// its bytes_sent from before the move (0 when it did not move).
+
+struct SenderLane {
+    using Entry = cts_tcp_sender_state;
+    using Tick = cts_tcp_sender_tick;
+    static constexpr bool kPaced = false, kTwoWay = false;
+    Entry* senders;
+    uint32_t n_conns, stride, max_buffers;
+    uint64_t R = 0, was = 0;  // bytes left; bytes_sent before the move
+    uint32_t B = 0;           // buffer size
+
+    // The slots whatever the time; R and B of a running connection.
+    __device__ __forceinline__ uint32_t want(uint32_t c, uint32_t& code)
+    {
+        code = CTS_TCP_SENDER_SKIPPED;
+        R = 0u;
+        B = 0u;
+        if (c >= n_conns) return 0u;
+        B = senders[c].buffer_size;
+        if (B == 0u || B > stride) return 0u;
+        code = CTS_TCP_SENDER_ENDED;
+        const uint64_t sent = senders[c].bytes_sent, transfer = senders[c].transfer_bytes;
+        if (senders[c].finished != 0u || sent >= transfer) return 0u;
+        code = CTS_TCP_SENDER_SENT;
+        R = transfer - sent;
+        const uint64_t k = R / B + (R % B != 0u ? 1u : 0u);
+        return k < (uint64_t)max_buffers ? (uint32_t)k : max_buffers;
+    }
+    __device__ __forceinline__ bool move(uint32_t c, uint64_t t, uint64_t (&bytes)[2])
+    {
+        Entry* const e = senders + c;
+        was = e->bytes_sent;
+        const uint64_t full = t * B;  // t <= capacity < 2^32
+        bytes[0] = full < R ? full : R;
+        e->bytes_sent = was + bytes[0];
+        e->buffers_sent += t;
+        const bool ended = bytes[0] == R;
+        if (ended) e->finished = 1u;
+        return ended;
+    }
+    __device__ __forceinline__ uint64_t before() const { return was; }
+};
 
 }  // namespace
 
@@ -317,15 +511,7 @@ __global__ void __launch_bounds__(kBlock)
     tcp_sender_sums(const uint32_t* __restrict__ ids, uint32_t n, const cts_tcp_sender_state* __restrict__ senders,
                     uint32_t n_conns, uint32_t stride, uint32_t max_buffers, uint64_t* __restrict__ sums)
 {
-    __shared__ uint64_t wsum[kBlock / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
-    uint64_t want = 0;
-    if (i < n) {
-        uint32_t code, B;
-        uint64_t R;
-        want = tcp_sender_limit(senders, ids[i], n_conns, stride, max_buffers, code, R, B);
-    }
-    tile_sum_store(want, wsum, sums);
+    tcp_tick_sums(SenderLane{lane_table(senders), n_conns, stride, max_buffers}, ids, n, sums);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -334,85 +520,15 @@ __global__ void __launch_bounds__(kBlock)
                      const uint64_t* __restrict__ sums, uint64_t* __restrict__ prefix, uint64_t* __restrict__ before,
                      uint32_t* __restrict__ codes, cts_tcp_sender_tick* __restrict__ tick, uint64_t* __restrict__ sent_block)
 {
-    __shared__ uint64_t wsum[kBlock / 64];
-    __shared__ uint64_t ctr[kBlock / 64][kCounterCount];
-    __shared__ uint32_t red[kBlock / 64][5];
-    zero_counters<kBlock / 64>(ctr);
-    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
-    uint32_t code = CTS_TCP_SENDER_SENT, c = 0u, B = 0u;
-    uint64_t want = 0, R = 0;
-    if (i < n) {
-        c = ids[i];
-        want = tcp_sender_limit(senders, c, n_conns, stride, max_buffers, code, R, B);
-    }
-    uint64_t total;
-    const uint64_t p = sums[blockIdx.x] + tile_scan_exclusive(want, wsum, total);
-    uint64_t bytes = 0;
-    uint32_t buffers = 0, sent = 0, finished = 0, no_room = 0, skipped = 0;
-    if (i < n) {
-        prefix[i] = p;
-        const uint64_t pc = p < (uint64_t)capacity ? p : (uint64_t)capacity;
-        const uint64_t t = want < (uint64_t)capacity - pc ? want : (uint64_t)capacity - pc;
-        uint64_t was = 0;
-        if (code != CTS_TCP_SENDER_SENT) {
-            skipped = 1u;
-        } else if (t == 0u) {
-            no_room = 1u;
-            code = CTS_TCP_SENDER_NO_ROOM;
-        } else {
-            bool ended;
-            bytes = tcp_sender_move(senders + c, t, R, B, was, ended);
-            buffers = (uint32_t)t;
-            sent = 1u;
-            if (ended) {
-                finished = 1u;
-                code = CTS_TCP_SENDER_FINISHED;
-            }
-        }
-        before[i] = was;
-        if (codes != nullptr) codes[i] = code;
-    }
-    bytes = wave_sum64(bytes);
-    // buffers, connections_sent, _finished, _no_room, _skipped
-    const uint32_t words[5] = {wave_sum(buffers), wave_sum(sent), wave_sum(finished), wave_sum(no_room),
-                               wave_sum(skipped)};
-    if ((threadIdx.x & 63u) == 0u) {
-        uint64_t* const own = ctr[threadIdx.x >> 6];
-        own[0] = bytes;     // cts_counters_sent.bytes_sent (TcpStatusDetails.m_bytesSent, ctsIOPattern.cpp:510)
-        own[1] = words[0];  // .buffers_sent
-        own[2] = words[2];  // .connections_finished
-    }
-    apply_flush(words, bytes, red, wsum, ctr, sent_block, [&](uint32_t k) { return &tick->buffers + k; },
-                &tick->bytes);
-}
-
-// cts_tcp_senders_send's planning: three launches, the middle one the servers' single-workgroup scan
-hipError_t launch_tcp_sender_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
-                                  cts_tcp_sender_state* senders, uint32_t n_conns, uint32_t stride, uint32_t capacity,
-                                  uint32_t* codes, cts_tcp_sender_tick* tick, uint64_t* sent_counters,
-                                  const TcpSenderScratch& scratch, hipStream_t stream)
-{
-    if (n == 0) return hipSuccess;
-    const uint64_t tiles = plan_tiles(n);
-    tcp_sender_sums<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, senders, n_conns, stride, max_buffers,
-                                                            scratch.sums);
-    ms_server_scan<<<1, kBlock, 0, stream>>>(scratch.sums, tiles, scratch.prefix + n,
-                                             reinterpret_cast<uint32_t*>(tick));
-    tcp_sender_apply<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, senders, n_conns, stride, capacity,
-                                                             max_buffers, scratch.sums, scratch.prefix, scratch.before,
-                                                             codes, tick, sent_counters);
-    return hipGetLastError();
+    tcp_tick_apply(SenderLane{senders, n_conns, stride, max_buffers}, ids, n, capacity, sums, prefix, before, codes,
+                   tick, sent_block);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Paced TCP senders (cts_tcp_senders_send_paced): the plain tick with every listed connection's wanted slots cut to what
-// its 64-byte pace entry lets out at now_ms.
-//   tcp_paced_sums    the pace machine runs on a register copy, nothing is stored
-//   tcp_paced_scan    the 48-byte tick block zeroed and its next_due_ms set to INT64_MAX
-//   tcp_paced_apply   the machine again, p_i, the taken count t_i, the codes, both entries' updates, the tick with its
-//                     tail and the sent block
-// The descriptor pass and the fill are the plain tick's launches, unchanged: they read prefix, before and the tick
-// block's first 32 bytes.
+// its 64-byte pace entry lets out at now_ms. _sums runs the pace machine on a register copy and stores nothing; _apply
+// runs it again and moves both entries. The descriptor pass and the fill are the plain tick's launches, unchanged: they
+// read prefix, before and the tick block's first 32 bytes.
 
 namespace {
 
@@ -483,14 +599,16 @@ struct PaceRegs {
         return offset;
     }
 
-    // run(cap) of cts_tcp_senders.h; cap <= ceil(R / B), so bytes are left at every step. The loop's length differs
-    // from lane to lane: a wave takes as long as its longest lane.
-    __device__ __forceinline__ uint32_t run(int64_t now, uint32_t cap, uint64_t R, uint32_t B)
+    // The pacing walk, run(cap) of cts_tcp_senders.h and run_x(cap) of cts_tcp_exchange.h: up to cap sends at `now`,
+    // stopped by a task that is not due yet; the count of sends let out. next() is the next send's bytes, taken(bytes)
+    // follows every send that is let out (the exchange tick's may swap *this for the other direction's registers).
+    // The loop's length differs from lane to lane: a wave takes as long as its longest lane.
+    template <typename Next, typename Taken>
+    __device__ __forceinline__ uint32_t walk(int64_t now, uint32_t cap, Next next, Taken taken)
     {
         uint32_t count = 0;
-        uint64_t left = R;
         while (count < cap) {
-            const uint64_t size = left < (uint64_t)B ? left : (uint64_t)B;
+            const auto size = next();
             if (pending != 0u) {
                 if (now < due) break;
                 pending = 0u;
@@ -503,38 +621,49 @@ struct PaceRegs {
                 }
             }
             ++count;
-            left -= size;
+            taken(size);
         }
         return count;
     }
 };
 
-// Listed connection c's wanted slots at now_ms: the limit, or run(limit) on Q, a register copy of its pace entry.
-// paced = Q holds the entry and has been moved.
-__device__ __forceinline__ uint32_t tcp_paced_want(const cts_tcp_sender_state* __restrict__ senders,
-                                                   const cts_tcp_sender_pace* __restrict__ pace, uint32_t c,
-                                                   uint32_t n_conns, uint32_t stride, uint32_t max_buffers,
-                                                   int64_t now, uint32_t& code, uint64_t& R, uint32_t& B, PaceRegs& Q,
-                                                   bool& paced)
-{
-    paced = false;
-    const uint32_t limit = tcp_sender_limit(senders, c, n_conns, stride, max_buffers, code, R, B);
-    if (code != CTS_TCP_SENDER_SENT) return 0u;
-    Q.load(pace + c);
-    if (Q.unpaced()) return limit;
-    paced = true;
-    return Q.run(now, limit, R, B);
-}
+struct PacedSenderLane : SenderLane {
+    using Tick = cts_tcp_sender_paced_tick;
+    static constexpr bool kPaced = true;
+    cts_tcp_sender_pace* pace;
+    int64_t now;
+    PaceRegs Q{};  // a register copy of the connection's pace entry
+    bool paced = false;
 
-__device__ __forceinline__ int64_t wave_min64(int64_t v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const int64_t u = (int64_t)__shfl_xor((long long)v, off, 64);
-        v = u < v ? u : v;
+    // the walk of cap <= ceil(R / B) steps, so bytes are left at every step
+    __device__ __forceinline__ uint32_t run(uint32_t cap)
+    {
+        uint64_t left = R;
+        return Q.walk(
+            now, cap, [&] { return left < (uint64_t)B ? left : (uint64_t)B; }, [&](uint64_t size) { left -= size; });
     }
-    return v;
-}
+    // The plain want, or what the walk lets out of it at now.
+    __device__ __forceinline__ uint32_t want(uint32_t c, uint32_t& code)
+    {
+        paced = false;
+        const uint32_t limit = SenderLane::want(c, code);
+        if (code != CTS_TCP_SENDER_SENT) return 0u;
+        Q.load(pace + c);
+        if (Q.unpaced()) return limit;
+        paced = true;
+        return run(limit);
+    }
+    __device__ __forceinline__ void keep(uint32_t c) const { Q.save(pace + c); }
+    __device__ __forceinline__ void reload(uint32_t c) { Q.load(pace + c); }
+    __device__ __forceinline__ void rerun(uint32_t t) { (void)run(t); }
+    __device__ __forceinline__ void due_of(uint32_t& pending, int64_t& due) const
+    {
+        if (Q.pending != 0u) {
+            pending = 1u;
+            due = Q.due;
+        }
+    }
+};
 
 }  // namespace
 
@@ -543,30 +672,8 @@ __global__ void __launch_bounds__(kBlock)
                    const cts_tcp_sender_pace* __restrict__ pace, uint32_t n_conns, uint32_t stride,
                    uint32_t max_buffers, int64_t now, uint64_t* __restrict__ sums)
 {
-    __shared__ uint64_t wsum[kBlock / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
-    uint64_t want = 0;
-    if (i < n) {
-        uint32_t code, B;
-        uint64_t R;
-        PaceRegs Q{};
-        bool paced;
-        want = tcp_paced_want(senders, pace, ids[i], n_conns, stride, max_buffers, now, code, R, B, Q, paced);
-    }
-    tile_sum_store(want, wsum, sums);
-}
-
-// One workgroup. tick is 12 dwords (cts_tcp_sender_paced_tick); its next_due_ms starts at INT64_MAX.
-__global__ void __launch_bounds__(kBlock)
-    tcp_paced_scan(uint64_t* __restrict__ sums, uint64_t tiles, uint64_t* __restrict__ prefix_total,
-                   uint32_t* __restrict__ tick)
-{
-    __shared__ uint64_t wsum[kBlock / 64];
-    const uint64_t total = tile_sums_scan(sums, tiles, wsum);
-    if (threadIdx.x == 0u) *prefix_total = total;
-    constexpr uint32_t kDue = offsetof(cts_tcp_sender_paced_tick, next_due_ms) / 4u;
-    if (threadIdx.x < sizeof(cts_tcp_sender_paced_tick) / 4u)
-        tick[threadIdx.x] = threadIdx.x == kDue ? 0xFFFFFFFFu : threadIdx.x == kDue + 1u ? 0x7FFFFFFFu : 0u;
+    tcp_tick_sums(PacedSenderLane{{lane_table(senders), n_conns, stride, max_buffers}, lane_table(pace), now}, ids, n,
+                  sums);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -576,154 +683,69 @@ __global__ void __launch_bounds__(kBlock)
                     uint64_t* __restrict__ prefix, uint64_t* __restrict__ before, uint32_t* __restrict__ codes,
                     cts_tcp_sender_paced_tick* __restrict__ tick, uint64_t* __restrict__ sent_block)
 {
-    __shared__ uint64_t wsum[kBlock / 64];
-    __shared__ uint64_t ctr[kBlock / 64][kCounterCount];
-    __shared__ uint32_t red[kBlock / 64][7];
-    __shared__ int64_t due[kBlock / 64];
-    zero_counters<kBlock / 64>(ctr);
-    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
-    uint32_t code = CTS_TCP_SENDER_SENT, c = 0u, B = 0u;
-    uint64_t want = 0, R = 0;
-    PaceRegs Q{};
-    bool paced = false;
-    if (i < n) {
-        c = ids[i];
-        want = tcp_paced_want(senders, pace, c, n_conns, stride, max_buffers, now, code, R, B, Q, paced);
-    }
-    uint64_t total;
-    const uint64_t p = sums[blockIdx.x] + tile_scan_exclusive(want, wsum, total);
-    uint64_t bytes = 0;
-    int64_t my_due = kNoDue;
-    uint32_t buffers = 0, sent = 0, finished = 0, no_room = 0, skipped = 0, waiting = 0, pending = 0;
-    if (i < n) {
-        prefix[i] = p;
-        const uint64_t pc = p < (uint64_t)capacity ? p : (uint64_t)capacity;
-        const uint64_t t = want < (uint64_t)capacity - pc ? want : (uint64_t)capacity - pc;
-        uint64_t was = 0;
-        if (code != CTS_TCP_SENDER_SENT) {
-            skipped = 1u;
-        } else if (want == 0u) {
-            // pacing lets nothing out: the sender entry stays, the pace entry may hold a new pending task
-            waiting = 1u;
-            code = CTS_TCP_SENDER_WAITING;
-            Q.save(pace + c);
-        } else if (t == 0u) {
-            no_room = 1u;
-            code = CTS_TCP_SENDER_NO_ROOM;
-            if (paced) Q.load(pace + c);  // both entries stay: what counts below is the stored entry
-        } else {
-            if (paced) {
-                if (t < want) {  // cut by the capacity: the machine moves t steps from the stored entry
-                    Q.load(pace + c);
-                    (void)Q.run(now, (uint32_t)t, R, B);
-                }
-                Q.save(pace + c);
-            }
-            bool ended;
-            bytes = tcp_sender_move(senders + c, t, R, B, was, ended);
-            buffers = (uint32_t)t;
-            sent = 1u;
-            if (ended) {
-                finished = 1u;
-                code = CTS_TCP_SENDER_FINISHED;
-            }
-        }
-        if (skipped == 0u && Q.pending != 0u) {
-            pending = 1u;
-            my_due = Q.due;
-        }
-        before[i] = was;
-        if (codes != nullptr) codes[i] = code;
-    }
-    bytes = wave_sum64(bytes);
-    // buffers, connections_sent, _finished, _no_room, _skipped; then the tail's connections_waiting, _pending
-    const uint32_t words[7] = {wave_sum(buffers), wave_sum(sent),    wave_sum(finished), wave_sum(no_room),
-                               wave_sum(skipped), wave_sum(waiting), wave_sum(pending)};
-    my_due = wave_min64(my_due);
-    if ((threadIdx.x & 63u) == 0u) {
-        uint64_t* const own = ctr[threadIdx.x >> 6];
-        own[0] = bytes;     // cts_counters_sent.bytes_sent (TcpStatusDetails.m_bytesSent, ctsIOPattern.cpp:510)
-        own[1] = words[0];  // .buffers_sent
-        own[2] = words[2];  // .connections_finished
-        due[threadIdx.x >> 6] = my_due;
-    }
-    apply_flush(
-        words, bytes, red, wsum, ctr, sent_block,
-        [&](uint32_t k) { return k < 5u ? &tick->tick.buffers + k : &tick->connections_waiting + (k - 5u); },
-        &tick->tick.bytes);
-    apply_flush_due(due, &tick->next_due_ms, 8u);
-}
-
-// cts_tcp_senders_send_paced's planning: three launches, the middle one a single workgroup
-hipError_t launch_tcp_paced_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
-                                 cts_tcp_sender_state* senders, cts_tcp_sender_pace* pace, uint32_t n_conns,
-                                 int64_t now_ms, uint32_t stride, uint32_t capacity, uint32_t* codes,
-                                 cts_tcp_sender_paced_tick* tick, uint64_t* sent_counters,
-                                 const TcpPacedScratch& scratch, hipStream_t stream)
-{
-    if (n == 0) return hipSuccess;
-    const uint64_t tiles = plan_tiles(n);
-    tcp_paced_sums<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, senders, pace, n_conns, stride, max_buffers,
-                                                           now_ms, scratch.plain.sums);
-    tcp_paced_scan<<<1, kBlock, 0, stream>>>(scratch.plain.sums, tiles, scratch.plain.prefix + n,
-                                             reinterpret_cast<uint32_t*>(tick));
-    tcp_paced_apply<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, senders, pace, n_conns, stride, capacity,
-                                                            max_buffers, now_ms, scratch.plain.sums,
-                                                            scratch.plain.prefix, scratch.plain.before, codes, tick,
-                                                            sent_counters);
-    return hipGetLastError();
+    tcp_tick_apply(PacedSenderLane{{senders, n_conns, stride, max_buffers}, pace, now}, ids, n, capacity, sums, prefix,
+                   before, codes, tick, sent_block);
 }
 
 // ---------------------------------------------------------------------------------------------
 // The exchange tick (cts_tcp_exchange_send): Push, Pull, PushPull and Duplex connections from 64-byte entries. Listed
-// connection i wants w_i = min(max_buffers, N - buffers_sent) slots of its buffer sequence and takes t_i as the TCP
-// senders do; whose turn each buffer is follows from its index (cts_tcp_exchange_math.hpp), so the planning never
-// looks at a direction: the move asks the closed form where the entry stands t buffers on.
-//   tcp_exchange_sums    the wants
-//   tcp_exchange_scan    ms_server_scan with the 48-byte tick block zeroed
-//   tcp_exchange_apply   p_i, t_i, the codes, the entries' moves, the tick with its bytes by direction, the sent block
-// apply leaves every listed connection's buffers_sent from before the move in the scratch; tcp_exchange_descs
-// (cts_fill.hip) reads prefix, before and the tick.
+// connection i wants w_i = min(max_buffers, N - buffers_sent) slots of its buffer sequence; whose turn each buffer is
+// follows from its index (cts_tcp_exchange_math.hpp), so the planning never looks at a direction: the move asks the
+// closed form where the entry stands t buffers on. before[i] is the connection's buffers_sent from before the move;
+// tcp_exchange_descs (cts_fill.hip) reads prefix, before and the tick.
 
 namespace {
 
-// The slots listed connection c wants, its code when it sends nothing whatever the room, and of a running connection
-// the entry's constants S and its position m.
-__device__ __forceinline__ uint32_t tcp_exchange_limit(const cts_tcp_exchange_state* __restrict__ entries, uint32_t c,
-                                                       uint32_t n_conns, uint32_t stride, uint32_t max_buffers,
-                                                       uint32_t& code, ExchangeShape& S, uint64_t& m)
-{
-    code = CTS_TCP_SENDER_SKIPPED;
-    m = 0u;
-    if (c >= n_conns) return 0u;
-    S = exchange_shape(entries + c);
-    if (!exchange_shape_ok(S) || S.B > stride) return 0u;
-    code = CTS_TCP_SENDER_ENDED;
-    m = entries[c].buffers_sent;
-    if (entries[c].finished != 0u || m >= S.N) return 0u;
-    code = CTS_TCP_SENDER_SENT;
-    const uint64_t k = S.N - m;
-    return k < (uint64_t)max_buffers ? (uint32_t)k : max_buffers;
-}
+struct ExchangeLane {
+    using Entry = cts_tcp_exchange_state;
+    using Tick = cts_tcp_exchange_tick;
+    static constexpr bool kPaced = false, kTwoWay = true;
+    Entry* entries;
+    uint32_t n_conns, stride, max_buffers;
+    ExchangeShape S{};  // the entry's constants
+    uint64_t m = 0;     // its position
 
-// Entry e at position m takes t > 0 slots: the bytes it sends by direction; true = the sequence is complete. The only
-// step that knows how many slots a connection takes is the one that moves its entry: the bytes of buffers m .. m + t by
-// direction are the difference of two positions, whatever segment ends lie between, and the entry holds the position
-// at m (cts_tcp_exchange_init, _seek and this move keep it so).
-__device__ __forceinline__ bool tcp_exchange_move(cts_tcp_exchange_state* e, const ExchangeShape& S, uint64_t m,
-                                                  uint64_t t, uint64_t& bytes0, uint64_t& bytes1)
-{
-    uint64_t to[2];
-    exchange_position(S, m + t, to);
-    bytes0 = exchange_sub(to[0], e->bytes_sent[0]);
-    bytes1 = exchange_sub(to[1], e->bytes_sent[1]);
-    e->bytes_sent[0] += bytes0;
-    e->bytes_sent[1] += bytes1;
-    e->buffers_sent = m + t;
-    const bool ended = m + t == S.N;
-    if (ended) e->finished = 1u;
-    return ended;
-}
+    __device__ __forceinline__ uint32_t want(uint32_t c, uint32_t& code)
+    {
+        return limit(entries, c, n_conns, stride, max_buffers, code, S, m);
+    }
+    // want()'s body, static and over references: the compiler simplifies it before it is inlined, and over this->S the
+    // same text ends as branches that cost tcp_exchange_sums two more VGPRs (12 for 10)
+    static __device__ __forceinline__ uint32_t limit(const Entry* __restrict__ entries, uint32_t c, uint32_t n_conns,
+                                                     uint32_t stride, uint32_t max_buffers, uint32_t& code,
+                                                     ExchangeShape& S, uint64_t& m)
+    {
+        code = CTS_TCP_SENDER_SKIPPED;
+        m = 0u;
+        if (c >= n_conns) return 0u;
+        S = exchange_shape(entries + c);
+        if (!exchange_shape_ok(S) || S.B > stride) return 0u;
+        code = CTS_TCP_SENDER_ENDED;
+        m = entries[c].buffers_sent;
+        if (entries[c].finished != 0u || m >= S.N) return 0u;
+        code = CTS_TCP_SENDER_SENT;
+        const uint64_t k = S.N - m;
+        return k < (uint64_t)max_buffers ? (uint32_t)k : max_buffers;
+    }
+    // The bytes of buffers m .. m + t by direction are the difference of two positions, whatever segment ends lie
+    // between, and the entry holds the position at m (cts_tcp_exchange_init, _seek and this move keep it so).
+    __device__ __forceinline__ bool move(uint32_t c, uint64_t t, uint64_t (&bytes)[2])
+    {
+        Entry* const e = entries + c;
+        uint64_t to[2];
+        exchange_position(S, m + t, to);
+        bytes[0] = exchange_sub(to[0], e->bytes_sent[0]);
+        bytes[1] = exchange_sub(to[1], e->bytes_sent[1]);
+        e->bytes_sent[0] += bytes[0];
+        e->bytes_sent[1] += bytes[1];
+        e->buffers_sent = m + t;
+        const bool ended = m + t == S.N;
+        if (ended) e->finished = 1u;
+        return ended;
+    }
+    __device__ __forceinline__ uint64_t before() const { return m; }
+    static __device__ __forceinline__ uint64_t* dir_of(Tick* tick) { return tick->bytes_dir; }
+};
 
 }  // namespace
 
@@ -731,27 +753,7 @@ __global__ void __launch_bounds__(kBlock)
     tcp_exchange_sums(const uint32_t* __restrict__ ids, uint32_t n, const cts_tcp_exchange_state* __restrict__ entries,
                       uint32_t n_conns, uint32_t stride, uint32_t max_buffers, uint64_t* __restrict__ sums)
 {
-    __shared__ uint64_t wsum[kBlock / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
-    uint64_t want = 0;
-    if (i < n) {
-        uint32_t code;
-        ExchangeShape S{};
-        uint64_t m;
-        want = tcp_exchange_limit(entries, ids[i], n_conns, stride, max_buffers, code, S, m);
-    }
-    tile_sum_store(want, wsum, sums);
-}
-
-// One workgroup. tick is 12 dwords (cts_tcp_exchange_tick).
-__global__ void __launch_bounds__(kBlock)
-    tcp_exchange_scan(uint64_t* __restrict__ sums, uint64_t tiles, uint64_t* __restrict__ prefix_total,
-                      uint32_t* __restrict__ tick)
-{
-    __shared__ uint64_t wsum[kBlock / 64];
-    const uint64_t total = tile_sums_scan(sums, tiles, wsum);
-    if (threadIdx.x == 0u) *prefix_total = total;
-    if (threadIdx.x < sizeof(cts_tcp_exchange_tick) / 4u) tick[threadIdx.x] = 0u;
+    tcp_tick_sums(ExchangeLane{lane_table(entries), n_conns, stride, max_buffers}, ids, n, sums);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -761,96 +763,19 @@ __global__ void __launch_bounds__(kBlock)
                        uint32_t* __restrict__ codes, cts_tcp_exchange_tick* __restrict__ tick,
                        uint64_t* __restrict__ sent_block)
 {
-    __shared__ uint64_t wsum[kBlock / 64];
-    __shared__ uint64_t ctr[kBlock / 64][kCounterCount];
-    __shared__ uint32_t red[kBlock / 64][5];
-    __shared__ uint64_t dir[kBlock / 64][2];
-    zero_counters<kBlock / 64>(ctr);
-    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
-    uint32_t code = CTS_TCP_SENDER_SENT, c = 0u;
-    uint64_t want = 0, m = 0;
-    ExchangeShape S{};
-    if (i < n) {
-        c = ids[i];
-        want = tcp_exchange_limit(entries, c, n_conns, stride, max_buffers, code, S, m);
-    }
-    uint64_t total;
-    const uint64_t p = sums[blockIdx.x] + tile_scan_exclusive(want, wsum, total);
-    uint64_t bytes0 = 0, bytes1 = 0;
-    uint32_t buffers = 0, sent = 0, finished = 0, no_room = 0, skipped = 0;
-    if (i < n) {
-        prefix[i] = p;
-        const uint64_t pc = p < (uint64_t)capacity ? p : (uint64_t)capacity;
-        const uint64_t t = want < (uint64_t)capacity - pc ? want : (uint64_t)capacity - pc;
-        if (code != CTS_TCP_SENDER_SENT) {
-            skipped = 1u;
-        } else if (t == 0u) {
-            no_room = 1u;
-            code = CTS_TCP_SENDER_NO_ROOM;
-        } else {
-            buffers = (uint32_t)t;
-            sent = 1u;
-            if (tcp_exchange_move(entries + c, S, m, t, bytes0, bytes1)) {
-                finished = 1u;
-                code = CTS_TCP_SENDER_FINISHED;
-            }
-        }
-        before[i] = m;
-        if (codes != nullptr) codes[i] = code;
-    }
-    bytes0 = wave_sum64(bytes0);
-    bytes1 = wave_sum64(bytes1);
-    const uint64_t bytes = bytes0 + bytes1;
-    // buffers, connections_sent, _finished, _no_room, _skipped
-    const uint32_t words[5] = {wave_sum(buffers), wave_sum(sent), wave_sum(finished), wave_sum(no_room),
-                               wave_sum(skipped)};
-    if ((threadIdx.x & 63u) == 0u) {
-        uint64_t* const own = ctr[threadIdx.x >> 6];
-        own[0] = bytes;     // cts_counters_sent.bytes_sent (TcpStatusDetails.m_bytesSent of whichever side sent)
-        own[1] = words[0];  // .buffers_sent
-        own[2] = words[2];  // .connections_finished
-        dir[threadIdx.x >> 6][0] = bytes0;
-        dir[threadIdx.x >> 6][1] = bytes1;
-    }
-    apply_flush(words, bytes, red, wsum, ctr, sent_block, [&](uint32_t k) { return &tick->tick.buffers + k; },
-                &tick->tick.bytes);
-    apply_flush_dir(dir, tick->bytes_dir, 8u);
-}
-
-// cts_tcp_exchange_send's planning: three launches, the middle one a single workgroup
-hipError_t launch_tcp_exchange_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
-                                    cts_tcp_exchange_state* entries, uint32_t n_conns, uint32_t stride,
-                                    uint32_t capacity, uint32_t* codes, cts_tcp_exchange_tick* tick,
-                                    uint64_t* sent_counters, const TcpExchangeScratch& scratch, hipStream_t stream)
-{
-    if (n == 0) return hipSuccess;
-    const uint64_t tiles = plan_tiles(n);
-    tcp_exchange_sums<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, entries, n_conns, stride, max_buffers,
-                                                              scratch.plain.sums);
-    tcp_exchange_scan<<<1, kBlock, 0, stream>>>(scratch.plain.sums, tiles, scratch.plain.prefix + n,
-                                                reinterpret_cast<uint32_t*>(tick));
-    tcp_exchange_apply<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, entries, n_conns, stride, capacity,
-                                                               max_buffers, scratch.plain.sums, scratch.plain.prefix,
-                                                               scratch.plain.before, codes, tick, sent_counters);
-    return hipGetLastError();
+    tcp_tick_apply(ExchangeLane{entries, n_conns, stride, max_buffers}, ids, n, capacity, sums, prefix, before, codes,
+                   tick, sent_block);
 }
 
 // ---------------------------------------------------------------------------------------------
 // The paced exchange tick (cts_tcp_exchange_send_paced): the exchange tick with every listed connection's wanted slots
 // cut by run_x of cts_tcp_exchange.h, the pace machine's walk with each step taken on the pace entry of the next
-// buffer's direction (entry c + d x n_conns: the side that sends direction d).
-//   tcp_exchange_paced_sums    the walk on register copies, nothing is stored
-//   tcp_exchange_paced_scan    the 64-byte tick block zeroed and its next_due_ms set to INT64_MAX
-//   tcp_exchange_paced_apply   the walk again, p_i, t_i, the codes, the entry's move (tcp_exchange_move), the pace
-//                              entries' updates, the tick with bytes_dir and the tail, the sent block
+// buffer's direction (entry c + d x n_conns: the side that sends direction d). _sums walks on register copies and
+// stores nothing; _apply walks again and moves the entry and the pace entries.
 // The walk pays exchange_element's division once: an ExchangeCursor is seeded at m and moved by additions. A lane keeps
 // both directions' pace registers, `cur` for the next buffer's direction and `oth`, and swaps them when the direction
 // flips, so no register is ever indexed by a direction. tcp_exchange_descs and the fill follow unchanged: they read
-// prefix, before and the block's first 32 bytes.
-
-static_assert(sizeof(cts_tcp_exchange_paced_tick) == 64 && offsetof(cts_tcp_exchange_paced_tick, next_due_ms) == 48 &&
-                  offsetof(cts_tcp_exchange_paced_tick, connections_waiting) == 56,
-              "cts_tcp_exchange_paced_tick: an exchange tick and the paced tick's 16-byte tail");
+// prefix, before and the block's first 48 and 32 bytes.
 
 namespace {
 
@@ -876,51 +801,52 @@ struct ExchangePace {
     }
     __device__ __forceinline__ bool unpaced() const { return cur.unpaced() && (!two || oth.unpaced()); }
 
-    // run_x(cap) of cts_tcp_exchange.h; cap <= N - m. PaceRegs::run's loop with the size and the entry taken from the
-    // cursor. A wave takes as long as its longest lane.
+    // the walk of cap <= N - m steps, the size and the entry of each taken from the cursor
     __device__ __forceinline__ uint32_t run(int64_t now, uint32_t cap, const ExchangeShape& S)
     {
-        uint32_t count = 0;
-        while (count < cap) {
-            const uint32_t size = at.len(S);
-            if (cur.pending != 0u) {
-                if (now < cur.due) break;
-                cur.pending = 0u;
-            } else {
-                const int64_t off = cur.step(now, (int64_t)size);
-                if (off > 0) {
-                    cur.pending = 1u;
-                    cur.due = now + off;
-                    break;
+        return cur.walk(
+            now, cap, [&] { return at.len(S); },
+            [&](uint32_t size) {
+                if (at.advance(S, size)) {
+                    const PaceRegs was = cur;
+                    cur = oth;
+                    oth = was;
                 }
-            }
-            ++count;
-            if (at.advance(S, size)) {
-                const PaceRegs was = cur;
-                cur = oth;
-                oth = was;
-            }
-        }
-        return count;
+            });
     }
 };
 
-// Listed connection c's wanted slots at now_ms: the limit, or run_x(limit) on X, register copies of its pace entries.
-// paced = X holds the entries and has been moved.
-__device__ __forceinline__ uint32_t tcp_exchange_paced_want(const cts_tcp_exchange_state* __restrict__ entries,
-                                                            const cts_tcp_sender_pace* __restrict__ pace, uint32_t c,
-                                                            uint32_t n_conns, uint32_t stride, uint32_t max_buffers,
-                                                            int64_t now, uint32_t& code, ExchangeShape& S, uint64_t& m,
-                                                            ExchangePace& X, bool& paced)
-{
-    paced = false;
-    const uint32_t limit = tcp_exchange_limit(entries, c, n_conns, stride, max_buffers, code, S, m);
-    if (code != CTS_TCP_SENDER_SENT) return 0u;
-    X.load(pace, c, n_conns, S, m);
-    if (X.unpaced()) return limit;
-    paced = true;
-    return X.run(now, limit, S);
-}
+struct PacedExchangeLane : ExchangeLane {
+    using Tick = cts_tcp_exchange_paced_tick;
+    static constexpr bool kPaced = true;
+    cts_tcp_sender_pace* pace;
+    int64_t now;
+    ExchangePace X{};  // register copies of the connection's pace entries
+    bool paced = false;
+
+    // The plain want, or what the walk lets out of it at now.
+    __device__ __forceinline__ uint32_t want(uint32_t c, uint32_t& code)
+    {
+        paced = false;
+        const uint32_t limit = ExchangeLane::want(c, code);
+        if (code != CTS_TCP_SENDER_SENT) return 0u;
+        X.load(pace, c, n_conns, S, m);
+        if (X.unpaced()) return limit;
+        paced = true;
+        return X.run(now, limit, S);
+    }
+    __device__ __forceinline__ void keep(uint32_t c) const { X.save(pace, c, n_conns); }
+    __device__ __forceinline__ void reload(uint32_t c) { X.load(pace, c, n_conns, S, m); }
+    __device__ __forceinline__ void rerun(uint32_t t) { (void)X.run(now, t, S); }
+    // a connection counts once; of a table kept by this tick only the next buffer's entry can be pending
+    __device__ __forceinline__ void due_of(uint32_t& pending, int64_t& due) const
+    {
+        if (X.cur.pending != 0u) due = X.cur.due;
+        if (X.oth.pending != 0u && X.oth.due < due) due = X.oth.due;
+        pending = (X.cur.pending | X.oth.pending) != 0u ? 1u : 0u;
+    }
+    static __device__ __forceinline__ uint64_t* dir_of(Tick* tick) { return tick->tick.bytes_dir; }
+};
 
 }  // namespace
 
@@ -930,31 +856,8 @@ __global__ void __launch_bounds__(kBlock)
                             const cts_tcp_sender_pace* __restrict__ pace, uint32_t n_conns, uint32_t stride,
                             uint32_t max_buffers, int64_t now, uint64_t* __restrict__ sums)
 {
-    __shared__ uint64_t wsum[kBlock / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
-    uint64_t want = 0;
-    if (i < n) {
-        uint32_t code;
-        ExchangeShape S{};
-        uint64_t m;
-        ExchangePace X{};
-        bool paced;
-        want = tcp_exchange_paced_want(entries, pace, ids[i], n_conns, stride, max_buffers, now, code, S, m, X, paced);
-    }
-    tile_sum_store(want, wsum, sums);
-}
-
-// One workgroup. tick is 16 dwords (cts_tcp_exchange_paced_tick); its next_due_ms starts at INT64_MAX.
-__global__ void __launch_bounds__(kBlock)
-    tcp_exchange_paced_scan(uint64_t* __restrict__ sums, uint64_t tiles, uint64_t* __restrict__ prefix_total,
-                            uint32_t* __restrict__ tick)
-{
-    __shared__ uint64_t wsum[kBlock / 64];
-    const uint64_t total = tile_sums_scan(sums, tiles, wsum);
-    if (threadIdx.x == 0u) *prefix_total = total;
-    constexpr uint32_t kDue = offsetof(cts_tcp_exchange_paced_tick, next_due_ms) / 4u;
-    if (threadIdx.x < sizeof(cts_tcp_exchange_paced_tick) / 4u)
-        tick[threadIdx.x] = threadIdx.x == kDue ? 0xFFFFFFFFu : threadIdx.x == kDue + 1u ? 0x7FFFFFFFu : 0u;
+    tcp_tick_sums(PacedExchangeLane{{lane_table(entries), n_conns, stride, max_buffers}, lane_table(pace), now}, ids,
+                  n, sums);
 }
 
 __global__ void __launch_bounds__(kBlock)
@@ -965,109 +868,81 @@ __global__ void __launch_bounds__(kBlock)
                              uint64_t* __restrict__ before, uint32_t* __restrict__ codes,
                              cts_tcp_exchange_paced_tick* __restrict__ tick, uint64_t* __restrict__ sent_block)
 {
-    __shared__ uint64_t wsum[kBlock / 64];
-    __shared__ uint64_t ctr[kBlock / 64][kCounterCount];
-    __shared__ uint32_t red[kBlock / 64][7];
-    __shared__ uint64_t dir[kBlock / 64][2];
-    __shared__ int64_t due[kBlock / 64];
-    zero_counters<kBlock / 64>(ctr);
-    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
-    uint32_t code = CTS_TCP_SENDER_SENT, c = 0u;
-    uint64_t want = 0, m = 0;
-    ExchangeShape S{};
-    ExchangePace X{};
-    bool paced = false;
-    if (i < n) {
-        c = ids[i];
-        want = tcp_exchange_paced_want(entries, pace, c, n_conns, stride, max_buffers, now, code, S, m, X, paced);
-    }
-    uint64_t total;
-    const uint64_t p = sums[blockIdx.x] + tile_scan_exclusive(want, wsum, total);
-    uint64_t bytes0 = 0, bytes1 = 0;
-    int64_t my_due = kNoDue;
-    uint32_t buffers = 0, sent = 0, finished = 0, no_room = 0, skipped = 0, waiting = 0, pending = 0;
-    if (i < n) {
-        prefix[i] = p;
-        const uint64_t pc = p < (uint64_t)capacity ? p : (uint64_t)capacity;
-        const uint64_t t = want < (uint64_t)capacity - pc ? want : (uint64_t)capacity - pc;
-        if (code != CTS_TCP_SENDER_SENT) {
-            skipped = 1u;
-        } else if (want == 0u) {
-            // pacing lets nothing out: the entry stays, the next direction's pace entry may hold a new pending task
-            waiting = 1u;
-            code = CTS_TCP_SENDER_WAITING;
-            X.save(pace, c, n_conns);
-        } else if (t == 0u) {
-            no_room = 1u;
-            code = CTS_TCP_SENDER_NO_ROOM;
-            if (paced) X.load(pace, c, n_conns, S, m);  // all three entries stay: what counts below is what is stored
-        } else {
-            if (paced) {
-                if (t < want) {  // cut by the capacity: the machine moves t steps from the stored entries
-                    X.load(pace, c, n_conns, S, m);
-                    (void)X.run(now, (uint32_t)t, S);
-                }
-                X.save(pace, c, n_conns);
-            }
-            buffers = (uint32_t)t;
-            sent = 1u;
-            if (tcp_exchange_move(entries + c, S, m, t, bytes0, bytes1)) {
-                finished = 1u;
-                code = CTS_TCP_SENDER_FINISHED;
-            }
-        }
-        if (skipped == 0u) {
-            // a connection counts once; of a table kept by this tick only the next buffer's entry can be pending
-            if (X.cur.pending != 0u) my_due = X.cur.due;
-            if (X.oth.pending != 0u && X.oth.due < my_due) my_due = X.oth.due;
-            pending = (X.cur.pending | X.oth.pending) != 0u ? 1u : 0u;
-        }
-        before[i] = m;
-        if (codes != nullptr) codes[i] = code;
-    }
-    bytes0 = wave_sum64(bytes0);
-    bytes1 = wave_sum64(bytes1);
-    const uint64_t bytes = bytes0 + bytes1;
-    // buffers, connections_sent, _finished, _no_room, _skipped; then the tail's connections_waiting, _pending
-    const uint32_t words[7] = {wave_sum(buffers), wave_sum(sent),    wave_sum(finished), wave_sum(no_room),
-                               wave_sum(skipped), wave_sum(waiting), wave_sum(pending)};
-    my_due = wave_min64(my_due);
-    if ((threadIdx.x & 63u) == 0u) {
-        uint64_t* const own = ctr[threadIdx.x >> 6];
-        own[0] = bytes;     // cts_counters_sent.bytes_sent (TcpStatusDetails.m_bytesSent of whichever side sent)
-        own[1] = words[0];  // .buffers_sent
-        own[2] = words[2];  // .connections_finished
-        dir[threadIdx.x >> 6][0] = bytes0;
-        dir[threadIdx.x >> 6][1] = bytes1;
-        due[threadIdx.x >> 6] = my_due;
-    }
-    apply_flush(
-        words, bytes, red, wsum, ctr, sent_block,
-        [&](uint32_t k) { return k < 5u ? &tick->tick.tick.buffers + k : &tick->connections_waiting + (k - 5u); },
-        &tick->tick.tick.bytes);
-    apply_flush_dir(dir, tick->tick.bytes_dir, 8u);
-    apply_flush_due(due, &tick->next_due_ms, 10u);
+    tcp_tick_apply(PacedExchangeLane{{entries, n_conns, stride, max_buffers}, pace, now}, ids, n, capacity, sums,
+                   prefix, before, codes, tick, sent_block);
 }
 
-// cts_tcp_exchange_send_paced's planning: three launches, the middle one a single workgroup
-hipError_t launch_tcp_exchange_paced_plan(const uint32_t* conn_ids, uint32_t n, uint32_t max_buffers,
-                                          cts_tcp_exchange_state* entries, cts_tcp_sender_pace* pace,
-                                          uint32_t n_conns, int64_t now_ms, uint32_t stride, uint32_t capacity,
-                                          uint32_t* codes, cts_tcp_exchange_paced_tick* tick, uint64_t* sent_counters,
-                                          const TcpExchangePacedScratch& scratch, hipStream_t stream)
+// ---------------------------------------------------------------------------------------------
+// The four TCP ticks' planning (launch_tcp_plan of cts_internal.hpp): launch_plan over the tick's two kernels.
+
+namespace {
+
+template <typename Tick>
+struct TickKernels;
+template <>
+struct TickKernels<cts_tcp_sender_tick> {
+    static constexpr bool kPaced = false;
+    static constexpr auto sums = tcp_sender_sums;
+    static constexpr auto apply = tcp_sender_apply;
+};
+template <>
+struct TickKernels<cts_tcp_sender_paced_tick> {
+    static constexpr bool kPaced = true;
+    static constexpr auto sums = tcp_paced_sums;
+    static constexpr auto apply = tcp_paced_apply;
+};
+template <>
+struct TickKernels<cts_tcp_exchange_tick> {
+    static constexpr bool kPaced = false;
+    static constexpr auto sums = tcp_exchange_sums;
+    static constexpr auto apply = tcp_exchange_apply;
+};
+template <>
+struct TickKernels<cts_tcp_exchange_paced_tick> {
+    static constexpr bool kPaced = true;
+    static constexpr auto sums = tcp_exchange_paced_sums;
+    static constexpr auto apply = tcp_exchange_paced_apply;
+};
+
+}  // namespace
+
+template <typename Tick, typename Entry>
+hipError_t launch_tcp_plan(const TcpTickArgs& a, Entry* entries, Tick* tick, const TcpTickScratch<Tick>& scratch,
+                           hipStream_t stream)
 {
-    if (n == 0) return hipSuccess;
-    const uint64_t tiles = plan_tiles(n);
-    const TcpSenderScratch& plain = scratch.exchange.plain;
-    tcp_exchange_paced_sums<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, entries, pace, n_conns, stride,
-                                                                    max_buffers, now_ms, plain.sums);
-    tcp_exchange_paced_scan<<<1, kBlock, 0, stream>>>(plain.sums, tiles, plain.prefix + n,
-                                                      reinterpret_cast<uint32_t*>(tick));
-    tcp_exchange_paced_apply<<<(uint32_t)tiles, kBlock, 0, stream>>>(conn_ids, n, entries, pace, n_conns, stride,
-                                                                     capacity, max_buffers, now_ms, plain.sums,
-                                                                     plain.prefix, plain.before, codes, tick,
-                                                                     sent_counters);
-    return hipGetLastError();
+    using K = TickKernels<Tick>;
+    uint32_t max_at = kNoMaxWord;
+    if constexpr (K::kPaced) max_at = offsetof(Tick, next_due_ms) / 4u;
+    uint64_t* const sent = static_cast<uint64_t*>(a.sent_counters);
+    return launch_plan(
+        a.n, scratch.sums, scratch.prefix, tick, max_at, stream,
+        [&](uint32_t tiles) {
+            if constexpr (K::kPaced)
+                K::sums<<<tiles, kBlock, 0, stream>>>(a.conn_ids, a.n, entries, a.pace, a.n_conns, a.stride,
+                                                      a.max_buffers, a.now_ms, scratch.sums);
+            else
+                K::sums<<<tiles, kBlock, 0, stream>>>(a.conn_ids, a.n, entries, a.n_conns, a.stride, a.max_buffers,
+                                                      scratch.sums);
+        },
+        [&](uint32_t tiles) {
+            if constexpr (K::kPaced)
+                K::apply<<<tiles, kBlock, 0, stream>>>(a.conn_ids, a.n, entries, a.pace, a.n_conns, a.stride,
+                                                       a.capacity, a.max_buffers, a.now_ms, scratch.sums,
+                                                       scratch.prefix, scratch.before, a.codes, tick, sent);
+            else
+                K::apply<<<tiles, kBlock, 0, stream>>>(a.conn_ids, a.n, entries, a.n_conns, a.stride, a.capacity,
+                                                       a.max_buffers, scratch.sums, scratch.prefix, scratch.before,
+                                                       a.codes, tick, sent);
+        });
 }
+
+template hipError_t launch_tcp_plan(const TcpTickArgs&, cts_tcp_sender_state*, cts_tcp_sender_tick*,
+                                    const TcpTickScratch<cts_tcp_sender_tick>&, hipStream_t);
+template hipError_t launch_tcp_plan(const TcpTickArgs&, cts_tcp_sender_state*, cts_tcp_sender_paced_tick*,
+                                    const TcpTickScratch<cts_tcp_sender_paced_tick>&, hipStream_t);
+template hipError_t launch_tcp_plan(const TcpTickArgs&, cts_tcp_exchange_state*, cts_tcp_exchange_tick*,
+                                    const TcpTickScratch<cts_tcp_exchange_tick>&, hipStream_t);
+template hipError_t launch_tcp_plan(const TcpTickArgs&, cts_tcp_exchange_state*, cts_tcp_exchange_paced_tick*,
+                                    const TcpTickScratch<cts_tcp_exchange_paced_tick>&, hipStream_t);
 
 }  // namespace cts

@@ -18,8 +18,8 @@ import ctypes
 import numpy as np
 
 from ._lib import check, lib
-from .types import (DESC_DTYPE, TCP_EXCHANGE_DTYPE, TCP_EXCHANGE_PACED_TICK_DTYPE, TCP_EXCHANGE_TICK_DTYPE,
-                    TCP_SENDER_PACE_DTYPE)
+from .tcp_senders import _PaceTable, _TickTable
+from .types import TCP_EXCHANGE_DTYPE, TCP_EXCHANGE_PACED_TICK_DTYPE, TCP_EXCHANGE_TICK_DTYPE
 
 
 def _one(entry) -> np.ndarray:
@@ -102,9 +102,9 @@ def exchange_send_paced(engine, arena, stride: int, first_slot: int, capacity: i
               _nbytes(scratch) if scratch_bytes is None else scratch_bytes, _stream(stream)))
 
 
-class ExchangeTable:
-    """Many two-way TCP connections on one device: the entry table, a tick's scratch, the arena with its descriptors,
-    the codes, the tick block and the sent block, with the tick as a method.
+class ExchangeTable(_TickTable):
+    """Many two-way TCP connections on one device: the entry table (``entries``), a tick's scratch, the arena with its
+    descriptors, the codes, the tick block and the sent block, with the tick as a method.
 
     settings: (pattern, transfer_bytes, buffer_size, push_bytes, pull_bytes) per connection slot (the last two may be
     left out). The arena holds arena_slots slots of stride bytes (pre-filled with `fill`), a tick writes at most
@@ -112,77 +112,25 @@ class ExchangeTable:
     receive half, whose tables have ``n_receivers`` = 2 x n_conns slots; ``expected_bytes()`` is their
     dev_expected_bytes."""
 
-    def __init__(self, engine, settings, stride: int, capacity: int, arena_slots: int = None, device=None,
-                 fill: int = 0, max_listed: int = None):
-        import torch
+    _TABLE, _ENTRY_DTYPE, _TICK_DTYPE = "entries", TCP_EXCHANGE_DTYPE, TCP_EXCHANGE_TICK_DTYPE
+    _init = staticmethod(lambda setting: exchange_init(*setting))
+    _scratch_bytes = staticmethod(exchange_scratch_bytes)
 
-        self.engine = engine
-        self.device = device or "cuda:%d" % engine.device
-        self.fresh = np.zeros(len(settings), dtype=TCP_EXCHANGE_DTYPE)
-        for c, s in enumerate(settings):
-            self.fresh[c] = exchange_init(*s)
-        self.n_conns, self.stride, self.capacity = len(settings), stride, capacity
+    def __init__(self, engine, settings, stride: int, capacity: int, **kw):
+        super().__init__(engine, settings, stride, capacity, **kw)
         self.n_receivers = 2 * self.n_conns
-        self.arena_slots = capacity if arena_slots is None else arena_slots
-        words = max(1, self.n_conns) * (TCP_EXCHANGE_DTYPE.itemsize // 8)
-        self.entries = torch.zeros(words, dtype=torch.int64, device=self.device)
-        self.load(self.fresh)
-        self.max_listed = max(1, self.n_conns if max_listed is None else max_listed)
-        self.scratch = torch.zeros((exchange_scratch_bytes(self.max_listed) + 7) // 8, dtype=torch.int64,
-                                   device=self.device)
-        self.arena = torch.full((max(16, self.arena_slots * stride),), fill, dtype=torch.uint8, device=self.device)
-        self.descs = torch.zeros(max(1, capacity) * (DESC_DTYPE.itemsize // 8), dtype=torch.int64, device=self.device)
-        self.codes = torch.zeros(self.max_listed, dtype=torch.int32, device=self.device)
-        self.tick = torch.zeros(TCP_EXCHANGE_TICK_DTYPE.itemsize // 8, dtype=torch.int64, device=self.device)
-        self.sent = engine.new_counters()
 
     def send(self, conn_ids, max_buffers: int, first_slot: int = 0, stream=None, capacity: int = None) -> None:
         """One tick of conn_ids (uint32/int32 device tensor, distinct, at most max_listed of them)."""
-        from .engine import _nbytes
-
-        n = _nbytes(conn_ids) // 4
-        if n > self.codes.numel():
-            raise ValueError("%d ids listed, the table's codes and scratch hold %d" % (n, self.codes.numel()))
-        capacity = self.capacity if capacity is None else capacity
-        if capacity > self.capacity:
-            raise ValueError("capacity %d, the table's descriptors hold %d" % (capacity, self.capacity))
-        exchange_send(self.engine, self.arena, self.stride, first_slot, capacity, conn_ids, max_buffers, self.entries,
-                      self.n_conns, self.descs, self.scratch, codes=self.codes, tick=self.tick,
-                      sent_counters=self.sent, stream=stream)
-
-    def load(self, entries: np.ndarray) -> None:
-        """Write entries (TCP_EXCHANGE_DTYPE[n_conns]) over the table: a transfer resumed, or a test's preset."""
-        import torch
-
-        e = np.ascontiguousarray(entries, dtype=TCP_EXCHANGE_DTYPE)
-        if len(e) != self.n_conns:
-            raise ValueError("%d entries for a table of %d" % (len(e), self.n_conns))
-        if self.n_conns:
-            self.entries.copy_(torch.from_numpy(e.view(np.int64).copy()))
+        self._tick(exchange_send, conn_ids, max_buffers, first_slot, stream, capacity)
 
     def expected_bytes(self) -> np.ndarray:
         """uint64[2 x n_conns]: what every receiver gets in total, direction-0 receivers first."""
         return np.array([exchange_direction_bytes(e, d) for d in (0, 1) for e in self.fresh], dtype=np.uint64)
 
-    def descs_of(self, n: int):
-        """The descriptors of the last tick's first n buffers (a view)."""
-        return self.descs[: n * (DESC_DTYPE.itemsize // 8)]
 
-    def read(self):
-        """(entries TCP_EXCHANGE_DTYPE, codes uint32, tick: one TCP_EXCHANGE_TICK_DTYPE record) copied to the host."""
-        return (self.entries.cpu().numpy().view(TCP_EXCHANGE_DTYPE)[: self.n_conns],
-                self.codes.cpu().numpy().view(np.uint32), self.tick.cpu().numpy().view(TCP_EXCHANGE_TICK_DTYPE)[0])
-
-    def read_arena(self):
-        """(arena bytes, descriptors DESC_DTYPE[capacity]) copied to the host."""
-        return self.arena.cpu().numpy(), self.descs.cpu().numpy().view(DESC_DTYPE)[: self.capacity]
-
-    def read_sent(self, stream=None) -> dict:
-        return self.engine.read_counters_sent(self.sent, stream=stream)
-
-
-class PacedExchangeTable(ExchangeTable):
-    """An ExchangeTable with a pace entry per side of every connection slot and the paced tick.
+class PacedExchangeTable(ExchangeTable, _PaceTable):
+    """An ExchangeTable with a pace entry per side of every connection slot (``pace``) and the paced tick.
 
     pace_settings: per connection slot a pair (client, server) of dicts of tcp_senders.pace_init's keywords
     (bytes_per_second, period_ms, burst_count, burst_delay_ms; {} = unpaced): the client's pace direction 0, the
@@ -190,56 +138,14 @@ class PacedExchangeTable(ExchangeTable):
     first quantum starts at start_ms. ``send(conn_ids, max_buffers, now_ms)`` is one paced tick; the plain tick stays
     available as ``ExchangeTable.send(table, ...)`` over the same entries."""
 
+    _TICK_DTYPE, _PACE_SIDES = TCP_EXCHANGE_PACED_TICK_DTYPE, 2
+    _scratch_bytes = staticmethod(exchange_paced_scratch_bytes)
+
     def __init__(self, engine, settings, pace_settings, stride: int, capacity: int, start_ms: int = 0, **kw):
-        import torch
-
-        from .tcp_senders import pace_init
-
         super().__init__(engine, settings, stride, capacity, **kw)
-        if len(pace_settings) != self.n_conns:
-            raise ValueError("%d pace settings for a table of %d" % (len(pace_settings), self.n_conns))
-        self.fresh_pace = np.zeros(2 * self.n_conns, dtype=TCP_SENDER_PACE_DTYPE)
-        for c, sides in enumerate(pace_settings):
-            for d in (0, 1):
-                self.fresh_pace[c + d * self.n_conns] = pace_init(start_ms=start_ms, **sides[d])
-        words = max(1, 2 * self.n_conns) * (TCP_SENDER_PACE_DTYPE.itemsize // 8)
-        self.pace = torch.zeros(words, dtype=torch.int64, device=self.device)
-        self.load_pace(self.fresh_pace)
-        self.scratch = torch.zeros((exchange_paced_scratch_bytes(self.max_listed) + 7) // 8, dtype=torch.int64,
-                                   device=self.device)
-        self.tick = torch.zeros(TCP_EXCHANGE_PACED_TICK_DTYPE.itemsize // 8, dtype=torch.int64, device=self.device)
+        self._init_pace(pace_settings, start_ms)
 
     def send(self, conn_ids, max_buffers: int, now_ms: int, first_slot: int = 0, stream=None,
              capacity: int = None) -> None:
         """One paced tick of conn_ids (uint32/int32 device tensor, distinct, at most max_listed of them) at now_ms."""
-        from .engine import _nbytes
-
-        n = _nbytes(conn_ids) // 4
-        if n > self.codes.numel():
-            raise ValueError("%d ids listed, the table's codes and scratch hold %d" % (n, self.codes.numel()))
-        capacity = self.capacity if capacity is None else capacity
-        if capacity > self.capacity:
-            raise ValueError("capacity %d, the table's descriptors hold %d" % (capacity, self.capacity))
-        exchange_send_paced(self.engine, self.arena, self.stride, first_slot, capacity, conn_ids, max_buffers,
-                            self.entries, self.pace, self.n_conns, now_ms, self.descs, self.scratch, codes=self.codes,
-                            tick=self.tick, sent_counters=self.sent, stream=stream)
-
-    def load_pace(self, pace: np.ndarray) -> None:
-        """Write pace (TCP_SENDER_PACE_DTYPE[2 x n_conns]) over the pace table."""
-        import torch
-
-        q = np.ascontiguousarray(pace, dtype=TCP_SENDER_PACE_DTYPE)
-        if len(q) != 2 * self.n_conns:
-            raise ValueError("%d pace entries for a table of %d connections" % (len(q), self.n_conns))
-        if self.n_conns:
-            self.pace.copy_(torch.from_numpy(q.view(np.int64).copy()))
-
-    def read(self):
-        """(entries, codes uint32, tick: one TCP_EXCHANGE_PACED_TICK_DTYPE record) copied to the host."""
-        return (self.entries.cpu().numpy().view(TCP_EXCHANGE_DTYPE)[: self.n_conns],
-                self.codes.cpu().numpy().view(np.uint32),
-                self.tick.cpu().numpy().view(TCP_EXCHANGE_PACED_TICK_DTYPE)[0])
-
-    def read_pace(self) -> np.ndarray:
-        """The pace table (TCP_SENDER_PACE_DTYPE[2 x n_conns]) copied to the host."""
-        return self.pace.cpu().numpy().view(TCP_SENDER_PACE_DTYPE)[: 2 * self.n_conns]
+        self._tick(exchange_send_paced, conn_ids, max_buffers, first_slot, stream, capacity, now_ms=now_ms)

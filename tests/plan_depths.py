@@ -31,7 +31,7 @@ import numpy as np
 import launch_depths as L
 
 TILE = 256           # listed connections per tile (kPlanTile)
-SCAN_BLOCK = 256     # tile sums per pass of ms_server_scan / tcp_paced_scan (kBlock)
+SCAN_BLOCK = 256     # tile sums per pass of tick_plan_scan (kBlock)
 WAVE = 64
 RING_BATCH = L.RING_BATCH
 M32, M64 = (1 << 32) - 1, (1 << 64) - 1
@@ -62,7 +62,7 @@ def tile_sums(w, defect=None):
 
 
 def scan(sums, defect=None):
-    """ms_server_scan / tcp_paced_scan: (exclusive scan of the tile sums, the carry entering each pass, grand total)."""
+    """tick_plan_scan: (exclusive scan of the tile sums, the carry entering each pass, grand total)."""
     out, carries, carry = [], [], 0
     for base in range(0, len(sums), SCAN_BLOCK):
         if defect == "no_carry" and base > 0:

@@ -50,7 +50,7 @@ def _tcp_facts(engine, w, capacity):
 
 
 def _same_prefix(table, prefix, wants, where):
-    """The scratch's first n + 1 words (MsServerScratch / TcpSenderScratch: prefix[0 .. n]) against the model's."""
+    """The scratch's first n + 1 words (MsServerScratch / TcpTickScratch: prefix[0 .. n]) against the model's."""
     n = len(prefix)
     got = table.scratch[: n + 1].cpu().numpy().view(np.uint64)
     assert np.array_equal(got[:n], np.asarray(prefix, dtype=np.uint64)), where

@@ -207,7 +207,7 @@ def test_seeked_past_2_pow_33(engine):
 
 # ---- 5: the scan's second pass -------------------------------------------------------------------------------------
 def test_65537_listed_connections(engine):
-    """65 537 listed one-buffer connections at stride 16: 257 tiles, so tcp_exchange_scan takes a second pass of one
+    """65 537 listed one-buffer connections at stride 16: 257 tiles, so tick_plan_scan takes a second pass of one
     tile; the patterns by turns, a pull or an odd direction in every tile."""
     n = 65537
     settings = [(c % 4, 1 + c % 16, 16, 1 + c % 5, 1 + c % 3) for c in range(n)]
