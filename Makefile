@@ -1,7 +1,7 @@
 # Build the MI355X engine (gfx950) and the CPU oracle.
 #   make            -> ctstraffic_amd/libcts_engine.so (the product: one kernel per path) + oracle/libcts_oracle.so +
 #                      the C++ device samples (ctstraffic_amd/build/device_verify, device_connections,
-#                      device_ms_connections, device_ms_servers, device_tcp_senders, device_tcp_paced_senders,
+#                      device_ms_connections, device_ms_servers, device_ms_servers_timed, device_tcp_senders, device_tcp_paced_senders,
 #                      device_tcp_exchange, device_tcp_paced_exchange) + what bench.py
 #                      and the tests run
 #                      (tools/libcts_bench_multi.so, tools/pattern_cpu_probe)
@@ -25,6 +25,7 @@ DEVICE_VERIFY := ctstraffic_amd/build/device_verify
 DEVICE_CONNECTIONS := ctstraffic_amd/build/device_connections
 DEVICE_MS_CONNECTIONS := ctstraffic_amd/build/device_ms_connections
 DEVICE_MS_SERVERS := ctstraffic_amd/build/device_ms_servers
+DEVICE_MS_SERVERS_TIMED := ctstraffic_amd/build/device_ms_servers_timed
 DEVICE_TCP_SENDERS := ctstraffic_amd/build/device_tcp_senders
 DEVICE_TCP_PACED_SENDERS := ctstraffic_amd/build/device_tcp_paced_senders
 DEVICE_TCP_EXCHANGE := ctstraffic_amd/build/device_tcp_exchange
@@ -35,7 +36,7 @@ PROBES := tools/hbm_read_ceiling tools/verify_ablation tools/mailbox_probe tools
           tools/first_read_probe
 BENCH_MULTI := tools/libcts_bench_multi.so
 
-all: $(ENGINE_SO) oracle $(DEVICE_VERIFY) $(DEVICE_CONNECTIONS) $(DEVICE_MS_CONNECTIONS) $(DEVICE_MS_SERVERS) $(DEVICE_TCP_SENDERS) $(DEVICE_TCP_PACED_SENDERS) $(DEVICE_TCP_EXCHANGE) $(DEVICE_TCP_PACED_EXCHANGE) $(BENCH_MULTI) tools/pattern_cpu_probe
+all: $(ENGINE_SO) oracle $(DEVICE_VERIFY) $(DEVICE_CONNECTIONS) $(DEVICE_MS_CONNECTIONS) $(DEVICE_MS_SERVERS) $(DEVICE_MS_SERVERS_TIMED) $(DEVICE_TCP_SENDERS) $(DEVICE_TCP_PACED_SENDERS) $(DEVICE_TCP_EXCHANGE) $(DEVICE_TCP_PACED_EXCHANGE) $(BENCH_MULTI) tools/pattern_cpu_probe
 
 probes: $(PROBES)
 
@@ -124,6 +125,11 @@ $(DEVICE_MS_CONNECTIONS): tests/cpp/device_ms_connections.cpp $(ENGINE_SO) $(wil
 
 # C++ MediaStream servers-into-clients sample against the C ABI (run on the GPU box by tests/test_cpp_ms_servers.py)
 $(DEVICE_MS_SERVERS): tests/cpp/device_ms_servers.cpp $(ENGINE_SO) $(wildcard include/*.h)
+	@mkdir -p ctstraffic_amd/build
+	$(HIPCC) -O2 -std=c++17 -Iinclude $< -o $@ -Lctstraffic_amd -lcts_engine -Wl,-rpath,'$$ORIGIN/..'
+
+# C++ MediaStream servers-by-the-clock sample against the C ABI (run on the GPU box by tests/test_cpp_ms_servers_timed.py)
+$(DEVICE_MS_SERVERS_TIMED): tests/cpp/device_ms_servers_timed.cpp $(ENGINE_SO) $(wildcard include/*.h)
 	@mkdir -p ctstraffic_amd/build
 	$(HIPCC) -O2 -std=c++17 -Iinclude $< -o $@ -Lctstraffic_amd -lcts_engine -Wl,-rpath,'$$ORIGIN/..'
 

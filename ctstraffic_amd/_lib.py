@@ -242,6 +242,13 @@ def _declare(L: ctypes.CDLL) -> None:
         "cts_media_stream_servers_scratch_bytes": ([u32], ctypes.c_size_t),
         "cts_media_stream_servers_send": ([P, P, u64, u32, u64, u32, P, u32, P, u32, ctypes.c_int64, ctypes.c_int64,
                                            P, P, P, P, P, P, ctypes.c_size_t, P], i32),
+        "cts_ms_server_schedule_init": ([P, ctypes.c_int64, P], i32),
+        "cts_media_stream_servers_timed_scratch_bytes": ([u32], ctypes.c_size_t),
+        "cts_ms_server_frames_due": ([P, P, ctypes.c_int64, u32, ctypes.POINTER(u32),
+                                      ctypes.POINTER(ctypes.c_int64)], i32),
+        "cts_media_stream_servers_send_at": ([P, P, u64, u32, u64, u32, P, u32, P, P, u32, u32, ctypes.c_int64,
+                                              ctypes.c_int64, ctypes.c_int64, P, P, P, P, P, P, ctypes.c_size_t, P],
+                                             i32),
         "cts_tcp_sender_init": ([u64, u32, P], i32),
         "cts_tcp_senders_scratch_bytes": ([u32], ctypes.c_size_t),
         "cts_tcp_senders_send": ([P, P, u64, u32, u64, u32, P, u32, u32, P, u32, P, P, P, P, P, ctypes.c_size_t, P],

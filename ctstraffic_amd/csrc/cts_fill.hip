@@ -443,62 +443,24 @@ __global__ void __launch_bounds__(kBlock)
                           cts_buf_desc* __restrict__ descs, uint32_t* __restrict__ lengths, uint32_t full_slots,
                           uint32_t capacity, uint32_t n_conns)
 {
-    constexpr uint32_t WAVES = kBlock / 64;
-    __shared__ RingHeader hs[kRingBatch];
-    __shared__ uint32_t ls[kRingBatch];
-    __shared__ uint64_t ps[kRingBatch + 1];
-    __shared__ uint64_t first_listed;
-    // (the clamp, and the id check below, only matter to a caller who lists a connection twice: nothing is written
-    // outside the capacity or read outside the table then either)
-    const uint32_t total = tick->datagrams < capacity ? tick->datagrams : capacity;
-    if (total == 0u) return;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t cps = stride >> 4;  // chunks per slot
-    // at least a batch's worth of datagrams per workgroup, or all of them
-    const uint32_t even = (uint32_t)(((uint64_t)total + gridDim.x - 1u) / gridDim.x);
-    const uint32_t least = total < kRingBatch ? total : kRingBatch;
-    const uint32_t per_wg = even > least ? even : least;
-    const uint64_t g0 = (uint64_t)blockIdx.x * per_wg;
-    if (g0 >= total) return;
-    const uint64_t g1 = g0 + per_wg < total ? g0 + per_wg : total;
-    if (threadIdx.x == 0u) first_listed = ms_server_listed(prefix, 0u, n, g0);
-    u32x4* const ring = reinterpret_cast<u32x4*>(ring_base);
-    for (uint64_t d0 = g0; d0 < g1; d0 += kRingBatch) {
-        const uint32_t nb = (uint32_t)(g1 - d0 < kRingBatch ? g1 - d0 : kRingBatch);
-        __syncthreads();  // every wave is done with the previous batch's LDS
-        const uint64_t i0 = first_listed;
-        for (uint32_t t = threadIdx.x; t <= kRingBatch; t += kBlock) ps[t] = prefix[i0 + t < n ? i0 + t : n];
-        __syncthreads();
-        for (uint32_t t = threadIdx.x; t < nb; t += kBlock) {
-            const uint64_t g = d0 + t;
-            uint32_t lo = 0u, hi = kRingBatch + 1u;  // the last w with ps[w] <= g; ps[0] <= d0
-            while (hi - lo > 1u) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (ps[mid] <= g) lo = mid;
-                else hi = mid;
-            }
-            uint64_t i = i0 + lo, p = ps[lo];
-            if (lo == kRingBatch && i + 1u < n) {
-                i = ms_server_listed(prefix, i, n, g);
-                p = prefix[i];
-            }
-            if (i >= n) i = n - 1u;  // (never, unless a connection is listed twice)
-            const uint32_t c = ids[i];
-            const cts_ms_server_state* e = servers + (c < n_conns ? c : 0u);
-            const uint32_t len = c >= n_conns ? 0u
-                                              : ms_server_length(e->frame_size_bytes, e->datagram_max_size,
-                                                                 e->datagrams_per_frame, (uint32_t)(g - p));
-            hs[t] = RingHeader{(uint64_t)(e->current_frame - 1), qpc, qpf};
-            ls[t] = len;
-            if (descs != nullptr)
-                descs[g] = cts_buf_desc{(first_slot + g) * stride, len, 0u, c, CTS_UDP_DATA_HEADER_LENGTH};
-            if (lengths != nullptr) lengths[g] = len;
-            if (t == nb - 1u) first_listed = i;
-        }
-        __syncthreads();
-#include "cts_ring_store_loop.hpp"
-    }
+    constexpr bool TIMED = false;
+    const uint64_t* const before = nullptr;  // (the fragment names it in the branch this kernel does not have)
+#include "cts_ms_server_fill_body.hpp"
+}
+
+// The timed tick's ring fill (cts_media_stream_servers_send_at): the same body over a connection's several frames.
+// before[i] is listed connection i's current_frame from before the planning moved its entry.
+template <bool NTS, bool SCALAR>
+__global__ void __launch_bounds__(kBlock)
+    ms_server_timed_fill(uint8_t* __restrict__ ring_base, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
+                         const uint32_t* __restrict__ ids, uint32_t n,
+                         const cts_ms_server_state* __restrict__ servers, const uint64_t* __restrict__ prefix,
+                         const uint64_t* __restrict__ before, const cts_ms_server_tick* __restrict__ tick,
+                         uint64_t qpc, uint64_t qpf, cts_buf_desc* __restrict__ descs, uint32_t* __restrict__ lengths,
+                         uint32_t full_slots, uint32_t capacity, uint32_t n_conns)
+{
+    constexpr bool TIMED = true;
+#include "cts_ms_server_fill_body.hpp"
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -665,12 +627,15 @@ hipError_t launch_media_stream_fill_strided(uint8_t* arena, uint64_t arena_bytes
     return hipGetLastError();
 }
 
-// the tick's ring fill: launch_media_stream_fill_strided's grid rule over the capacity (the total is on the device)
-hipError_t launch_ms_server_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
-                                 uint32_t capacity, const uint32_t* conn_ids, uint32_t n,
-                                 const cts_ms_server_state* servers, uint32_t n_conns, const uint64_t* prefix,
-                                 const cts_ms_server_tick* tick, int64_t qpc, int64_t qpf, cts_buf_desc* descs,
-                                 uint32_t* lengths, hipStream_t stream, const LaunchGeometry& geo)
+// the tick's ring fill: launch_media_stream_fill_strided's grid rule over the capacity (the total is on the device);
+// before == nullptr is the plain tick's kernel, otherwise the timed tick's
+static hipError_t launch_ms_server_fill_of(uint8_t* arena, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
+                                           uint32_t capacity, const uint32_t* conn_ids, uint32_t n,
+                                           const cts_ms_server_state* servers, uint32_t n_conns,
+                                           const uint64_t* prefix, const uint64_t* before,
+                                           const cts_ms_server_tick* tick, int64_t qpc, int64_t qpf,
+                                           cts_buf_desc* descs, uint32_t* lengths, hipStream_t stream,
+                                           const LaunchGeometry& geo)
 {
     if (n == 0 || capacity == 0) return hipSuccess;
     if ((stride & 15u) != 0u || stride < 32u || stride > (1u << 20) || ((uintptr_t)arena & 15u) != 0u ||
@@ -684,12 +649,39 @@ hipError_t launch_ms_server_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t 
     const uint32_t full_slots = (uint32_t)(slots < 0xFFFFFFFFull ? slots : 0xFFFFFFFFull);
     with_flags(
         [&](auto NTS, auto SCALAR) {
-            ms_server_fill<NTS.value, SCALAR.value><<<grid, kBlock, 0, stream>>>(
-                ring, ring_bytes, stride, first_slot, conn_ids, n, servers, prefix, tick, (uint64_t)qpc, (uint64_t)qpf,
-                descs, lengths, full_slots, capacity, n_conns);
+            if (before == nullptr)
+                ms_server_fill<NTS.value, SCALAR.value><<<grid, kBlock, 0, stream>>>(
+                    ring, ring_bytes, stride, first_slot, conn_ids, n, servers, prefix, tick, (uint64_t)qpc,
+                    (uint64_t)qpf, descs, lengths, full_slots, capacity, n_conns);
+            else
+                ms_server_timed_fill<NTS.value, SCALAR.value><<<grid, kBlock, 0, stream>>>(
+                    ring, ring_bytes, stride, first_slot, conn_ids, n, servers, prefix, before, tick, (uint64_t)qpc,
+                    (uint64_t)qpf, descs, lengths, full_slots, capacity, n_conns);
         },
         geo.fill_nt != 0, stride >= 1024u);
     return hipGetLastError();
+}
+
+hipError_t launch_ms_server_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
+                                 uint32_t capacity, const uint32_t* conn_ids, uint32_t n,
+                                 const cts_ms_server_state* servers, uint32_t n_conns, const uint64_t* prefix,
+                                 const cts_ms_server_tick* tick, int64_t qpc, int64_t qpf, cts_buf_desc* descs,
+                                 uint32_t* lengths, hipStream_t stream, const LaunchGeometry& geo)
+{
+    return launch_ms_server_fill_of(arena, arena_bytes, stride, first_slot, capacity, conn_ids, n, servers, n_conns,
+                                    prefix, nullptr, tick, qpc, qpf, descs, lengths, stream, geo);
+}
+
+hipError_t launch_ms_server_timed_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
+                                       uint32_t capacity, const uint32_t* conn_ids, uint32_t n,
+                                       const cts_ms_server_state* servers, uint32_t n_conns, const uint64_t* prefix,
+                                       const uint64_t* before, const cts_ms_server_tick* tick, int64_t qpc, int64_t qpf,
+                                       cts_buf_desc* descs, uint32_t* lengths, hipStream_t stream,
+                                       const LaunchGeometry& geo)
+{
+    if (before == nullptr) return hipErrorInvalidValue;
+    return launch_ms_server_fill_of(arena, arena_bytes, stride, first_slot, capacity, conn_ids, n, servers, n_conns,
+                                    prefix, before, tick, qpc, qpf, descs, lengths, stream, geo);
 }
 
 // the tick's descriptors: one lane per slot of the capacity, at most the verify path's grid (the total is on the device)

@@ -277,6 +277,27 @@ static_assert(TcpTickScratch<cts_tcp_exchange_paced_tick>::bytes(0) == 72 &&
                   TcpTickScratch<cts_tcp_exchange_paced_tick>::bytes(257) == 4200,
               "cts_tcp_exchange_paced_scratch_bytes");
 
+// The servers' timed tick (cts_media_stream_servers_send_at) has the TCP ticks' scratch: the word per listed connection
+// is its current_frame from before the move, the block a cts_ms_server_timed_tick.
+using MsServerTimedScratch = TcpTickScratch<cts_ms_server_timed_tick>;
+static_assert(MsServerTimedScratch::bytes(0) == 56 && MsServerTimedScratch::bytes(1) == 80 &&
+                  MsServerTimedScratch::bytes(256) == 4160 && MsServerTimedScratch::bytes(257) == 4184,
+              "cts_media_stream_servers_timed_scratch_bytes");
+// The timed planning is launch_ms_server_plan with every connection's frames cut to what its schedule entry releases
+// at now_ms and at most max_frames; it also writes scratch.before. The timed fill is launch_ms_server_fill with the
+// frame of every datagram taken from before[] and its tick-local index: a connection may send several frames.
+hipError_t launch_ms_server_timed_plan(const uint32_t* conn_ids, uint32_t n, cts_ms_server_state* servers,
+                                       const cts_ms_server_schedule* schedule, uint32_t n_conns, uint32_t stride,
+                                       uint32_t capacity, uint32_t max_frames, int64_t now_ms, uint32_t* codes,
+                                       cts_ms_server_timed_tick* tick, uint64_t* udp_counters,
+                                       const MsServerTimedScratch& scratch, hipStream_t stream);
+hipError_t launch_ms_server_timed_fill(uint8_t* arena, uint64_t arena_bytes, uint32_t stride, uint64_t first_slot,
+                                       uint32_t capacity, const uint32_t* conn_ids, uint32_t n,
+                                       const cts_ms_server_state* servers, uint32_t n_conns, const uint64_t* prefix,
+                                       const uint64_t* before, const cts_ms_server_tick* tick, int64_t qpc, int64_t qpf,
+                                       cts_buf_desc* descs, uint32_t* lengths, hipStream_t stream,
+                                       const LaunchGeometry& geo);
+
 // Every tick block begins with the plain tick's 32 bytes, which the fill reads, and a paced exchange block with the
 // exchange tick's 48, which the exchange descriptor pass reads.
 #if defined(__HIP__)

@@ -1,6 +1,7 @@
 // cts_ring_store_loop.hpp — the store loop of one staged batch of a datagram ring. A fragment, not a header: it is
-// included inside the batch loop of media_stream_fill_ring_kernel and of ms_server_fill (cts_fill.hip), so
-// that both kernels run one loop and the compiler sees, in each of them, the text it saw before the second one
+// included inside the batch loop of media_stream_fill_ring_kernel (cts_fill.hip) and of ms_server_fill and
+// ms_server_timed_fill (cts_ms_server_fill_body.hpp), so
+// that these kernels run one loop and the compiler sees, in each of them, the text it saw before the second one
 // existed (a function taking the LDS arrays changed the first kernel's instructions).
 //
 // In scope where it is included:

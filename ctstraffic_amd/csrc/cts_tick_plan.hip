@@ -1,11 +1,11 @@
 // cts_tick_plan.hip — the planning of a device-resident sender's tick for gfx950: which ring slots every listed
-// connection takes, with no pattern byte written. Five ticks plan the same way (cts_media_stream_servers_send,
+// connection takes, with no pattern byte written. Six ticks plan the same way (cts_media_stream_servers_send, _send_at,
 // cts_tcp_senders_send, cts_tcp_senders_send_paced, cts_tcp_exchange_send, cts_tcp_exchange_send_paced): listed
 // connection i wants w_i slots (0 when it sends nothing whatever the room); p_i, the exclusive 64-bit prefix of the
 // wants in listed order, is its first slot, and the room left at p_i decides what it takes. Three plain launches in
 // tiles of kPlanTile listed connections (no workgroup ever waits for another), issued by launch_plan:
 //   *_sums          each tile's sum of wants                              -> sums[tile]
-//   tick_plan_scan  one workgroup, one kernel for all five ticks: exclusive scan of the tile sums in place in passes
+//   tick_plan_scan  one workgroup, one kernel for all six ticks: exclusive scan of the tile sums in place in passes
 //                   of kBlock tiles, prefix[n] = the grand total, the tick block initialised
 //   *_apply         p_i = sums[tile] + the tile's own scan -> prefix[i]; the code, the entries' updates, the tick block
 //                   and the counter block
@@ -13,6 +13,8 @@
 // scan kernel, the three launches). Then
 //   ms_server_sums / _apply   the MediaStream servers, with a body of their own: a connection sends its whole frame or
 //                             nothing, and the tick moves another kind of entry
+//   ms_server_timed_sums / _apply
+//                             the same servers by the clock: whole frames, as many as the schedule has released
 //   tcp_tick_sums / _apply    the frame of the four TCP ticks, written once over a lane type: the index, the scan, the
 //                             clamp to the capacity, the ladder of codes, the stores, the wave sums, the sent block and
 //                             the tick block with its tails
@@ -25,11 +27,12 @@
 //   tcp_sender_ / tcp_paced_ / tcp_exchange_ / tcp_exchange_paced_ sums and apply: the frame over one lane type each
 // What writes the ring from prefix[] is in cts_fill.hip, beside the loops it shares with the other fills.
 // Scratch (MsServerScratch, TcpTickScratch<Tick> of cts_internal.hpp): u64 prefix[n + 1], u64 sums[tiles], for the TCP
-// ticks u64 before[n], and a tick.
+// ticks and the servers' timed tick u64 before[n], and a tick.
 #include <hip/hip_runtime.h>
 
 #include "cts_chunks.hpp"
 #include "cts_internal.hpp"
+#include "cts_ms_server_schedule_math.hpp"
 #include "cts_tcp_exchange_math.hpp"
 
 namespace cts {
@@ -43,6 +46,12 @@ static_assert(sizeof(cts_tcp_sender_paced_tick) == 48 && offsetof(cts_tcp_sender
 static_assert(sizeof(cts_tcp_exchange_paced_tick) == 64 && offsetof(cts_tcp_exchange_paced_tick, next_due_ms) == 48 &&
                   offsetof(cts_tcp_exchange_paced_tick, connections_waiting) == 56,
               "cts_tcp_exchange_paced_tick: an exchange tick and the paced tick's 16-byte tail");
+
+static_assert(sizeof(cts_ms_server_schedule) == 16 && alignof(cts_ms_server_schedule) == 8, "cts_ms_server_schedule: 16 bytes");
+static_assert(sizeof(cts_ms_server_timed_tick) == 48 && offsetof(cts_ms_server_timed_tick, next_due_ms) == 32 &&
+                  offsetof(cts_ms_server_timed_tick, connections_waiting) == 40 &&
+                  offsetof(cts_ms_server_timed_tick, frames) == 44,
+              "cts_ms_server_timed_tick: a plain tick and 16 bytes");
 
 namespace {
 
@@ -307,6 +316,174 @@ hipError_t launch_ms_server_plan(const uint32_t* conn_ids, uint32_t n, cts_ms_se
         [&](uint32_t tiles) {
             ms_server_apply<<<tiles, kBlock, 0, stream>>>(conn_ids, n, servers, n_conns, stride, capacity,
                                                           scratch.sums, scratch.prefix, codes, tick, udp_counters);
+        });
+}
+
+// ---------------------------------------------------------------------------------------------
+// The servers' timed tick (cts_media_stream_servers_send_at): the plain tick with every listed connection's frames
+// those that its schedule entry releases at now (cts_ms_server_schedule_math.hpp: two divisions, no loop over
+// frames), at most max_frames of them. Listed connection i wants w_i = min(wf_i x k_i, UINT32_MAX) slots and takes t_i
+// = min(wf_i, room / k_i) whole frames, so a connection cut by the capacity has pushed every later prefix past the
+// capacity and the tick's datagrams are still the slots [0, total) with no gap. before[i] is the connection's
+// current_frame from before the move; ms_server_timed_fill (cts_fill.hip) reads prefix, before and the entries.
+
+namespace {
+
+// The frames listed connection c wants (0 with its code when it sends nothing whatever the room; code 5 when no frame
+// is out) and its k. The schedule entry is read for a running connection only.
+__device__ __forceinline__ uint32_t ms_server_timed_want(const cts_ms_server_state* __restrict__ servers,
+                                                         const cts_ms_server_schedule* __restrict__ schedule,
+                                                         uint32_t c, uint32_t n_conns, uint32_t stride,
+                                                         uint32_t max_frames, int64_t now, uint32_t& code, uint32_t& k)
+{
+    // the plain tick's codes 4, 2 and 4 first, as ms_server_want decides them
+    code = CTS_MS_SERVER_SKIPPED;
+    k = 0u;
+    if (c >= n_conns) return 0u;
+    if (servers[c].finished != 0u) {
+        code = CTS_MS_SERVER_ENDED;
+        return 0u;
+    }
+    if (servers[c].datagram_max_size > stride) return 0u;
+    code = CTS_MS_SERVER_SENT;
+    k = servers[c].datagrams_per_frame;
+    const uint32_t fps = schedule[c].frames_per_second;
+    const uint32_t wf = ms_schedule_frames(schedule[c].base_time_ms, fps != 0u ? fps : 1u, servers[c].current_frame,
+                                           servers[c].final_frame, now, max_frames);
+    if (wf == 0u) code = CTS_MS_SERVER_WAITING;
+    return wf;
+}
+
+// w = min(wf x k, UINT32_MAX): the cap keeps the 64-bit prefix from wrapping over 2^32 listed connections
+// (returned as 32 bits from the product's halves: with a 64-bit minimum here the compiler swapped the operands of one
+// add in ms_server_sums, and tools/kernel_text.py no longer showed that kernel as the one before this tick existed)
+__device__ __forceinline__ uint32_t ms_server_timed_slots(uint32_t wf, uint32_t k)
+{
+    const uint64_t w = (uint64_t)wf * k;
+    return (uint32_t)(w >> 32) != 0u ? 0xFFFFFFFFu : (uint32_t)w;
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(kBlock)
+    ms_server_timed_sums(const uint32_t* __restrict__ ids, uint32_t n, const cts_ms_server_state* __restrict__ servers,
+                         const cts_ms_server_schedule* __restrict__ schedule, uint32_t n_conns, uint32_t stride,
+                         uint32_t max_frames, int64_t now, uint64_t* __restrict__ sums)
+{
+    __shared__ uint64_t wsum[kBlock / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
+    uint64_t want = 0;
+    if (i < n) {
+        uint32_t code, k;
+        const uint32_t wf = ms_server_timed_want(servers, schedule, ids[i], n_conns, stride, max_frames, now, code, k);
+        want = ms_server_timed_slots(wf, k);
+    }
+    tile_sum_store(want, wsum, sums);
+}
+
+__global__ void __launch_bounds__(kBlock)
+    ms_server_timed_apply(const uint32_t* __restrict__ ids, uint32_t n, cts_ms_server_state* __restrict__ servers,
+                          const cts_ms_server_schedule* __restrict__ schedule, uint32_t n_conns, uint32_t stride,
+                          uint32_t capacity, uint32_t max_frames, int64_t now, const uint64_t* __restrict__ sums,
+                          uint64_t* __restrict__ prefix, uint64_t* __restrict__ before, uint32_t* __restrict__ codes,
+                          cts_ms_server_timed_tick* __restrict__ tick, uint64_t* __restrict__ udp)
+{
+    // datagrams, connections_sent, _finished, _no_room, _skipped; then the tail's connections_waiting, frames
+    constexpr int WORDS = 7;
+    constexpr uint32_t kDueAt = 8u;  // apply_flush keeps threads 0 .. WORDS busy
+    static_assert(WORDS < (int)kDueAt, "next_due_ms's thread lies past apply_flush's");
+    __shared__ uint64_t wsum[kBlock / 64];
+    __shared__ uint64_t ctr[kBlock / 64][kCounterCount];
+    __shared__ uint32_t red[kBlock / 64][WORDS];
+    __shared__ int64_t due[kBlock / 64];
+    zero_counters<kBlock / 64>(ctr);
+    const uint64_t i = (uint64_t)blockIdx.x * kPlanTile + threadIdx.x;
+    uint32_t code = CTS_MS_SERVER_SENT, c = 0u, k = 0u, wf = 0u;
+    if (i < n) {
+        c = ids[i];
+        wf = ms_server_timed_want(servers, schedule, c, n_conns, stride, max_frames, now, code, k);
+    }
+    uint64_t total;
+    const uint64_t p = sums[blockIdx.x] + tile_scan_exclusive(ms_server_timed_slots(wf, k), wsum, total);
+    uint64_t bytes = 0;
+    int64_t my_due = kNoDue;
+    uint32_t datagrams = 0, sent = 0, finished = 0, no_room = 0, skipped = 0, waiting = 0, frames = 0;
+    if (i < n) {
+        prefix[i] = p;
+        uint64_t was = 0;
+        if (code == CTS_MS_SERVER_WAITING) {
+            waiting = 1u;
+        } else if (code != CTS_MS_SERVER_SENT) {
+            skipped = 1u;
+        } else {
+            const uint32_t pc = p < (uint64_t)capacity ? (uint32_t)p : capacity;
+            const uint32_t fit = (capacity - pc) / (k != 0u ? k : 1u);
+            const uint32_t t = wf < fit ? wf : fit;
+            if (t == 0u) {
+                no_room = 1u;
+                code = CTS_MS_SERVER_NO_ROOM;
+            } else {
+                // the only step that knows how many frames the connection takes is the one that moves its entry
+                cts_ms_server_state* e = servers + c;
+                bytes = (uint64_t)t * e->frame_size_bytes;  // t x F <= capacity x stride < 2^52
+                datagrams = t * k;                         // <= capacity
+                frames = t;
+                sent = 1u;
+                e->bits_sent += 8u * bytes;
+                e->datagrams_sent += datagrams;
+                was = (uint64_t)e->current_frame;
+                const int64_t next = e->current_frame + (int64_t)t;
+                e->current_frame = next;
+                if (next > e->final_frame) {
+                    e->finished = 1u;
+                    finished = 1u;
+                    code = CTS_MS_SERVER_FINISHED;
+                }
+            }
+        }
+        // what the tick leaves running: the time of its next frame
+        if (skipped == 0u && finished == 0u) {
+            const uint32_t fps = schedule[c].frames_per_second;
+            my_due = ms_schedule_due(schedule[c].base_time_ms, fps != 0u ? fps : 1u, servers[c].current_frame);
+        }
+        before[i] = was;
+        if (codes != nullptr) codes[i] = code;
+    }
+    bytes = wave_sum64(bytes);
+    const uint32_t words[WORDS] = {wave_sum(datagrams), wave_sum(sent),    wave_sum(finished), wave_sum(no_room),
+                                   wave_sum(skipped),   wave_sum(waiting), wave_sum(frames)};
+    my_due = wave_min64(my_due);
+    if ((threadIdx.x & 63u) == 0u) {
+        // the reference's server adds its sent bits to UdpStatusDetails.m_bitsReceived (ctsIOPattern.cpp:1162)
+        ctr[threadIdx.x >> 6][0] = 8u * bytes;                 // cts_counters_udp.bits_received
+        ctr[threadIdx.x >> 6][kCounterCount - 1] = words[0];  // cts_counters_udp.datagrams
+        due[threadIdx.x >> 6] = my_due;
+    }
+    apply_flush(
+        words, bytes, red, wsum, ctr, udp,
+        [&](uint32_t w) { return w < 5u ? &tick->tick.datagrams + w : &tick->connections_waiting + (w - 5u); },
+        &tick->tick.bytes);
+    apply_flush_due(due, &tick->next_due_ms, kDueAt);
+}
+
+// cts_media_stream_servers_send_at's planning
+hipError_t launch_ms_server_timed_plan(const uint32_t* conn_ids, uint32_t n, cts_ms_server_state* servers,
+                                       const cts_ms_server_schedule* schedule, uint32_t n_conns, uint32_t stride,
+                                       uint32_t capacity, uint32_t max_frames, int64_t now_ms, uint32_t* codes,
+                                       cts_ms_server_timed_tick* tick, uint64_t* udp_counters,
+                                       const MsServerTimedScratch& scratch, hipStream_t stream)
+{
+    return launch_plan(
+        n, scratch.sums, scratch.prefix, tick, (uint32_t)(offsetof(cts_ms_server_timed_tick, next_due_ms) / 4u), stream,
+        [&](uint32_t tiles) {
+            ms_server_timed_sums<<<tiles, kBlock, 0, stream>>>(conn_ids, n, servers, schedule, n_conns, stride,
+                                                               max_frames, now_ms, scratch.sums);
+        },
+        [&](uint32_t tiles) {
+            ms_server_timed_apply<<<tiles, kBlock, 0, stream>>>(conn_ids, n, servers, schedule, n_conns, stride,
+                                                                capacity, max_frames, now_ms, scratch.sums,
+                                                                scratch.prefix, scratch.before, codes, tick,
+                                                                udp_counters);
         });
 }
 

@@ -528,6 +528,56 @@ def servers_send(engine, arena, stride: int, first_slot: int, capacity: int, con
               _nbytes(scratch) if scratch_bytes is None else scratch_bytes, _stream(stream)))
 
 
+def server_schedule_init(frames_per_second: int, base_time_ms: int) -> np.ndarray:
+    """cts_ms_server_schedule_init: a schedule entry (one MS_SERVER_SCHEDULE_DTYPE record) for a server of this frame
+    rate whose frame 0 is due at base_time_ms. Raises CtsError for frames_per_second == 0 or a base outside
+    [0, 2^62)."""
+    from .types import MS_SERVER_SCHEDULE_DTYPE
+
+    s = Settings(0, 0, frames_per_second, 0, 0)
+    out = np.zeros(1, dtype=MS_SERVER_SCHEDULE_DTYPE)
+    check("cts_ms_server_schedule_init",
+          lib().cts_ms_server_schedule_init(ctypes.addressof(s), base_time_ms, out.ctypes.data))
+    return out[0]
+
+
+def server_frames_due(state, schedule, now_ms: int, max_frames: int):
+    """cts_ms_server_frames_due: (frames, next_due_ms) of one entry and its schedule entry (records of
+    MS_SERVER_STATE_DTYPE and MS_SERVER_SCHEDULE_DTYPE) at now_ms: the closed form on the host."""
+    from .types import MS_SERVER_SCHEDULE_DTYPE, MS_SERVER_STATE_DTYPE
+
+    e = np.array([state], dtype=MS_SERVER_STATE_DTYPE)
+    q = np.array([schedule], dtype=MS_SERVER_SCHEDULE_DTYPE)
+    frames, due = ctypes.c_uint32(0), ctypes.c_int64(0)
+    check("cts_ms_server_frames_due",
+          lib().cts_ms_server_frames_due(e.ctypes.data, q.ctypes.data, now_ms, max_frames, ctypes.byref(frames),
+                                         ctypes.byref(due)))
+    return int(frames.value), int(due.value)
+
+
+def servers_timed_scratch_bytes(n: int) -> int:
+    """cts_media_stream_servers_timed_scratch_bytes: the scratch a timed tick over n listed connections needs."""
+    return int(lib().cts_media_stream_servers_timed_scratch_bytes(n))
+
+
+def servers_send_at(engine, arena, stride: int, first_slot: int, capacity: int, conn_ids, servers, schedule,
+                    n_conns: int, max_frames: int, now_ms: int, qpc: int, qpf: int, scratch, descs=None, lengths=None,
+                    codes=None, tick=None, udp_counters=None, stream=None, n: int = None, arena_bytes: int = None,
+                    scratch_bytes: int = None) -> None:
+    """cts_media_stream_servers_send_at: one timed tick of the connections conn_ids at now_ms, at most max_frames
+    frames of each. servers_send's arguments, and schedule (16 bytes per connection slot, a device tensor); tick is 48
+    bytes. Raises CtsError(CTS_E_INVALID) for a refused argument."""
+    from .engine import _nbytes, _stream
+
+    n = _nbytes(conn_ids) // 4 if n is None else n
+    check("cts_media_stream_servers_send_at",
+          engine._L.cts_media_stream_servers_send_at(
+              engine._h, _ptr(arena), _nbytes(arena) if arena_bytes is None else arena_bytes, stride, first_slot,
+              capacity, _ptr(conn_ids), n, _ptr(servers), _ptr(schedule), n_conns, max_frames, now_ms, qpc, qpf,
+              _ptr(descs), _ptr(lengths), _ptr(codes), _ptr(tick), _ptr(udp_counters), _ptr(scratch),
+              _nbytes(scratch) if scratch_bytes is None else scratch_bytes, _stream(stream)))
+
+
 class ServerTable:
     """Many MediaStream servers on one device: the entry table, a tick's scratch, the datagram ring with its
     descriptors and lengths, the codes, the tick block and the UDP block, with the tick as a method.
@@ -536,10 +586,13 @@ class ServerTable:
     ring_slots slots of stride bytes (pre-filled with `fill`), a tick writes at most capacity of them from first_slot
     on. :meth:`send` is one frame of the listed connections; ``descs_of(n)`` is the descriptor array of the tick's
     first n datagrams for :meth:`ConnectionTable.verify` and :meth:`ConnectionTable.accumulate`, with n computed from
-    the settings (``datagrams_per_tick``): nothing is read back between the send and the receive pass."""
+    the settings (``datagrams_per_tick``): nothing is read back between the send and the receive pass.
+
+    schedule: (frames_per_second, base_time_ms) per connection slot (see :meth:`set_schedule`). With it
+    :meth:`send_at` is the tick by the clock: the frames of the listed connections that are due at now_ms."""
 
     def __init__(self, engine, settings, stride: int, capacity: int, ring_slots: int = None, device=None,
-                 fill: int = 0, max_listed: int = None):
+                 fill: int = 0, max_listed: int = None, schedule=None):
         import torch
 
         from .types import MS_SERVER_STATE_DTYPE, MS_SERVER_TICK_DTYPE
@@ -564,6 +617,61 @@ class ServerTable:
         self.codes = torch.zeros(self.max_listed, dtype=torch.int32, device=self.device)
         self.tick = torch.zeros(MS_SERVER_TICK_DTYPE.itemsize // 8, dtype=torch.int64, device=self.device)
         self.udp = engine.new_counters()
+        # the frame schedule (set_schedule) and what send_at needs beside it; the plain tick reads none of them
+        self.schedule = self.timed_scratch = self.timed_tick = None
+        if schedule is not None:
+            self.set_schedule(schedule)
+
+    def set_schedule(self, schedule) -> None:
+        """The table's frame schedule: (frames_per_second, base_time_ms) per connection slot, or an
+        MS_SERVER_SCHEDULE_DTYPE array of n_conns records written as it is (a test's preset). Needed before
+        :meth:`send_at`; the host may write it again at any time between ticks, no tick writes it."""
+        import torch
+
+        from .types import MS_SERVER_SCHEDULE_DTYPE, MS_SERVER_TIMED_TICK_DTYPE
+
+        if isinstance(schedule, np.ndarray) and schedule.dtype == MS_SERVER_SCHEDULE_DTYPE:
+            q = np.ascontiguousarray(schedule)
+        else:
+            q = np.zeros(len(schedule), dtype=MS_SERVER_SCHEDULE_DTYPE)
+            for c, (fps, base) in enumerate(schedule):
+                q[c] = server_schedule_init(fps, base)
+        if len(q) != self.n_conns:
+            raise ValueError("%d schedule entries for a table of %d" % (len(q), self.n_conns))
+        words = max(1, self.n_conns) * (MS_SERVER_SCHEDULE_DTYPE.itemsize // 8)
+        self.schedule = torch.zeros(words, dtype=torch.int64, device=self.device)
+        if self.n_conns:
+            self.schedule.copy_(torch.from_numpy(q.view(np.int64).copy()))
+        if self.timed_scratch is None:
+            self.timed_scratch = torch.zeros((servers_timed_scratch_bytes(self.max_listed) + 7) // 8,
+                                             dtype=torch.int64, device=self.device)
+            self.timed_tick = torch.zeros(MS_SERVER_TIMED_TICK_DTYPE.itemsize // 8, dtype=torch.int64,
+                                          device=self.device)
+
+    def send_at(self, conn_ids, now_ms: int, max_frames: int, qpc: int, qpf: int, first_slot: int = 0,
+                stream=None) -> None:
+        """One timed tick of conn_ids (uint32/int32 device tensor, distinct, at most max_listed of them): the frames
+        the schedule releases at now_ms, at most max_frames of each connection. :meth:`read_timed` has the tick block;
+        the codes, ring, descriptors, lengths and UDP block are the plain tick's arrays."""
+        from .engine import _nbytes
+
+        if self.schedule is None:
+            raise ValueError("send_at needs the table's schedule: set_schedule first")
+        n = _nbytes(conn_ids) // 4
+        if n > self.codes.numel():
+            raise ValueError("%d ids listed, the table's codes and scratch hold %d" % (n, self.codes.numel()))
+        servers_send_at(self.engine, self.ring, self.stride, first_slot, self.capacity, conn_ids, self.servers,
+                        self.schedule, self.n_conns, max_frames, now_ms, qpc, qpf, self.timed_scratch,
+                        descs=self.descs, lengths=self.lengths, codes=self.codes, tick=self.timed_tick,
+                        udp_counters=self.udp, stream=stream)
+
+    def read_timed(self):
+        """(entries, codes uint32, tick: one MS_SERVER_TIMED_TICK_DTYPE record) copied to the host, after send_at."""
+        from .types import MS_SERVER_TIMED_TICK_DTYPE
+
+        return (self.servers.cpu().numpy().view(self.fresh.dtype)[: self.n_conns],
+                self.codes.cpu().numpy().view(np.uint32),
+                self.timed_tick.cpu().numpy().view(MS_SERVER_TIMED_TICK_DTYPE)[0])
 
     def datagrams_per_tick(self, conn_ids) -> int:
         """The datagrams one tick of these (host) ids writes while all of them run and fit: the receive pass's n."""

@@ -157,6 +157,15 @@ MS_SERVER_TICK_DTYPE = np.dtype(
 MS_SERVER_SENT, MS_SERVER_FINISHED, MS_SERVER_ENDED, MS_SERVER_NO_ROOM, MS_SERVER_SKIPPED = 0, 1, 2, 3, 4
 MS_SERVER_MIN_DATAGRAM = 53  # CTS_MS_SERVER_MIN_DATAGRAM
 assert MS_SERVER_STATE_DTYPE.itemsize == 48 and MS_SERVER_TICK_DTYPE.itemsize == 32
+# cts_ms_server_schedule: one MediaStream server's frame schedule, beside its entry; the host writes it, no tick does
+MS_SERVER_SCHEDULE_DTYPE = np.dtype([("base_time_ms", "<i8"), ("frames_per_second", "<u4"), ("reserved", "<u4")])
+# cts_ms_server_timed_tick: what one cts_media_stream_servers_send_at did; its first 32 bytes are the plain tick's
+MS_SERVER_TIMED_TICK_DTYPE = np.dtype(
+    MS_SERVER_TICK_DTYPE.descr + [("next_due_ms", "<i8"), ("connections_waiting", "<u4"), ("frames", "<u4")]
+)
+MS_SERVER_WAITING = 5  # CTS_MS_SERVER_WAITING: running, but no frame is due at now_ms
+assert MS_SERVER_SCHEDULE_DTYPE.itemsize == 16 and MS_SERVER_TIMED_TICK_DTYPE.itemsize == 48
+assert MS_SERVER_TIMED_TICK_DTYPE.fields["next_due_ms"][1] == 32
 # cts_tcp_sender_state (include/cts_tcp_senders.h): one TCP sender's device entry
 TCP_SENDER_DTYPE = np.dtype(
     [

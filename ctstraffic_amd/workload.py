@@ -850,6 +850,104 @@ class MediaStreamServerView:
         self.codes, self.tick = codes, tick
         return codes, tick
 
+    def send_at(self, conn_ids, schedule: np.ndarray, now_ms: int, max_frames: int, qpc: int, qpf: int,
+                first_slot: int = 0, capacity: int = None):
+        """One timed tick (cts_media_stream_servers_send_at) of the distinct connections conn_ids at now_ms over
+        `schedule` (media_stream_server_schedule). The frames that are out are found as the reference finds them, one
+        frame after the other by its own expression and its "< 2" rule (media_stream_frames_out), not by the device's
+        closed form. Returns (codes, tick), the tick with MS_SERVER_TIMED_TICK_FIELDS."""
+        from .media_stream import split
+
+        capacity = self.capacity if capacity is None else capacity
+        e, tick = self.entries, dict.fromkeys(MS_SERVER_TIMED_TICK_FIELDS, 0)
+        tick["next_due_ms"] = INT64_MAX
+        codes, p = np.zeros(len(conn_ids), dtype=np.uint32), 0
+        for i, c in enumerate(int(x) for x in conn_ids):
+            if c >= self.n_conns or int(e["finished"][c]) != 0 or int(e["datagram_max_size"][c]) > self.stride:
+                codes[i] = 2 if c < self.n_conns and int(e["finished"][c]) != 0 else 4
+                tick["connections_skipped"] += 1
+                continue
+            F, M, k = (int(e[f][c]) for f in ("frame_size_bytes", "datagram_max_size", "datagrams_per_frame"))
+            base, fps = int(schedule["base_time_ms"][c]), int(schedule["frames_per_second"][c])
+            seq, final = int(e["current_frame"][c]), int(e["final_frame"][c])
+            wf = media_stream_frames_out(base, fps, seq, final, now_ms, max_frames)
+            t = 0
+            if wf == 0:
+                codes[i] = 5
+                tick["connections_waiting"] += 1
+            else:
+                first, p = p, p + min(wf * k, 0xFFFFFFFF)
+                t = min(wf, (capacity - min(first, capacity)) // k)
+                if t == 0:
+                    codes[i] = 3
+                    tick["connections_no_room"] += 1
+            if t:
+                lens = [int(x) for x in split(F, M)]
+                assert len(lens) == k and sum(lens) == F
+                for f in range(t):
+                    s0 = first_slot + first + f * k
+                    for j in range(k):
+                        o = (s0 + j) * self.stride
+                        self.ring[o:o + lens[j]] = media_stream_datagram(lens[j], seq + f, qpc, qpf)
+                d = self.descs[first:first + t * k]
+                d["byte_offset"] = (first_slot + first + np.arange(t * k, dtype=np.uint64)) * np.uint64(self.stride)
+                d["length"], d["expected_pattern_offset"], d["conn_index"] = lens * t, 0, c
+                d["skip_head"] = UDP_DATA_HEADER_LENGTH
+                self.lengths[first:first + t * k] = lens * t
+                e["bits_sent"][c] = int(e["bits_sent"][c]) + 8 * t * F
+                e["datagrams_sent"][c] = int(e["datagrams_sent"][c]) + t * k
+                e["current_frame"][c] = seq + t
+                if seq + t > final:
+                    e["finished"][c] = 1
+                    tick["connections_finished"] += 1
+                    codes[i] = 1
+                tick["bytes"] += t * F
+                tick["datagrams"] += t * k
+                tick["frames"] += t
+                tick["connections_sent"] += 1
+                self.udp["bits_received"] += 8 * t * F
+                self.udp["datagrams"] += t * k
+            if codes[i] != 1:  # left running: when its next frame is due
+                tick["next_due_ms"] = min(tick["next_due_ms"], media_stream_frame_due(base, fps, seq + t))
+        self.codes, self.tick = codes, tick
+        return codes, tick
+
+
+INT64_MAX = (1 << 63) - 1
+MS_SERVER_TIMED_TICK_FIELDS = MS_SERVER_TICK_FIELDS + ("next_due_ms", "connections_waiting", "frames")
+
+
+def media_stream_server_schedule(settings):
+    """cts_ms_server_schedule_init as a model, for a list of (frames_per_second, base_time_ms). Returns
+    MS_SERVER_SCHEDULE_DTYPE[len(settings)]; raises ValueError where cts_ms_server_schedule_init returns
+    CTS_E_INVALID."""
+    from .types import MS_SERVER_SCHEDULE_DTYPE
+
+    q = np.zeros(len(settings), dtype=MS_SERVER_SCHEDULE_DTYPE)
+    for c, (fps, base) in enumerate(settings):
+        if fps == 0 or fps > 0xFFFFFFFF or not 0 <= base < (1 << 62):
+            raise ValueError("connection %d: %d frames per second from %d ms" % (c, fps, base))
+        q[c]["base_time_ms"], q[c]["frames_per_second"] = base, fps
+    return q
+
+
+def media_stream_frame_due(base_time_ms: int, frames_per_second: int, frame: int) -> int:
+    """When the reference sends frame `frame`: m_baseTimeMilliseconds + m_currentFrame * 1000LL / m_frameRateFps
+    (ctsIOPattern.cpp:1136-1150)."""
+    return base_time_ms + frame * 1000 // frames_per_second
+
+
+def media_stream_frames_out(base_time_ms: int, frames_per_second: int, current_frame: int, final_frame: int,
+                            now_ms: int, max_frames: int) -> int:
+    """How many frames from current_frame on the reference's server sends at now_ms without arming its timer, at most
+    max_frames: it sends the next frame at once while that frame's time offset is below 2
+    (ctsMediaStreamServerConnectedSocket.cpp:62-74). One frame after the other, as the reference goes."""
+    f = current_frame
+    while (f <= final_frame and f - current_frame < max_frames
+           and media_stream_frame_due(base_time_ms, frames_per_second, f) - now_ms < 2):
+        f += 1
+    return f - current_frame
+
 
 def media_stream_server_view(entries: np.ndarray, stride: int, ring: np.ndarray,
                              capacity: int) -> MediaStreamServerView:

@@ -9,6 +9,14 @@
  *
  *   per tick   cts_media_stream_servers_send(ids, ...)  -> one frame of every listed connection: the ring's datagrams,
  *                                                          their descriptors and lengths, the entries, a tick block
+ *        or    cts_media_stream_servers_send_at(ids, ..., now_ms)
+ *                                                       -> the frames of every listed connection that the reference's
+ *                                                          schedule (ctsIOPattern.cpp:1136-1150, the "< 2" rule of
+ *                                                          ctsMediaStreamServerConnectedSocket.cpp:62-74) releases at
+ *                                                          now_ms, from a 16-byte schedule entry per connection; the
+ *                                                          tick block ends with the time of the next frame
+ *
+ * so a run lists every connection in every tick and its one host timer sleeps until next_due_ms.
  *
  * and the receiving half consumes what it wrote: cts_media_stream_verify_status_at and
  * cts_media_stream_conns_accumulate over the descriptors, cts_media_stream_conns_render, cts_media_stream_conns_close.
@@ -21,10 +29,9 @@
  * Out of scope:
  *   - the connection-id datagram and the START exchange (39 bytes once per connection): they stay with the caller;
  *     CTS_PATTERN_MEDIA_STREAM (cts_pattern.h) makes them
- *   - the wall-clock schedule of the frames (m_timeOffsetMilliseconds): a tick is the caller's timer, as for
- *     cts_media_stream_conns_render
  *   - a ring that wraps: a tick writes the slots first_slot .. first_slot + datagrams of one flat arena
  *   - a qpc per connection: one tick carries one timestamp
+ *   - handing the written slots to sockets: the ring is the caller's to drain
  *
  * Conventions as cts_media_stream_conns.h: noexcept, int status, device pointers from hipMalloc, stream = hipStream_t
  * as void*. Every argument check comes before the engine is used, so a bad argument is CTS_E_INVALID with nothing
@@ -129,6 +136,93 @@ int cts_media_stream_servers_send(cts_engine* engine, void* dev_arena, uint64_t 
                                   cts_buf_desc* dev_descs, uint32_t* dev_lengths, uint32_t* dev_codes,
                                   cts_ms_server_tick* dev_tick, void* dev_udp_counters, void* dev_scratch,
                                   size_t scratch_bytes, void* stream);
+
+/* ---- The frame schedule on the device ----------------------------------------------------------------------------
+ * ctsIoPatternMediaStreamServer gives every frame send the time offset m_baseTimeMilliseconds + m_currentFrame x
+ * 1000LL / m_frameRateFps - now (ctsIOPattern.cpp:1136-1150), and ctsMediaStreamServerConnectedSocket sends at once
+ * when that offset is below 2 and arms a timer for it otherwise (.cpp:62-74, :125-133). The schedule has no state of
+ * its own: which frames are out at now_ms follows from the two numbers below and the entry's current_frame. */
+
+/* One per connection slot, beside dev_servers: device memory, 8-byte aligned, 16 bytes. The host writes it
+ * (cts_ms_server_schedule_init) and no tick ever writes it. */
+typedef struct cts_ms_server_schedule {
+    int64_t base_time_ms;       /* m_baseTimeMilliseconds: the time of frame 0, on the clock of now_ms; in [0, 2^62) */
+    uint32_t frames_per_second; /* m_frameRateFps, not 0 */
+    uint32_t reserved;
+} cts_ms_server_schedule;
+
+/* A schedule entry from the server's settings and the time its stream starts. CTS_E_INVALID for a null argument,
+ * frames_per_second == 0, or base_time_ms outside [0, 2^62). Host only. */
+int cts_ms_server_schedule_init(const cts_media_stream_settings* settings, int64_t base_time_ms,
+                                cts_ms_server_schedule* out);
+
+#define CTS_MS_SERVER_WAITING 5u /* running, but no frame is due at now_ms: nothing sent */
+
+/* What one timed tick did. 48 bytes, 8-byte aligned. Its first 32 bytes are the plain tick's block. */
+typedef struct cts_ms_server_timed_tick {
+    cts_ms_server_tick tick;
+    int64_t next_due_ms;          /* the smallest due(current_frame) of the listed connections that the tick leaves
+                                     running (codes 0, 3 and 5), after the tick; INT64_MAX when there is none. A value
+                                     <= now_ms + 1 means: tick again once the ring is drained */
+    uint32_t connections_waiting; /* code 5 */
+    uint32_t frames;              /* frames sent, all connections */
+} cts_ms_server_timed_tick;
+
+/* Bytes of dev_scratch a timed tick over n listed connections needs: the plain tick's (with the larger tick block) and
+ * a 64-bit word per listed connection, its current_frame from before the move. */
+size_t cts_media_stream_servers_timed_scratch_bytes(uint32_t n);
+
+/* The closed form on the host, for the caller's own bookkeeping: how many frames of entry E the schedule S releases at
+ * now_ms, at most max_frames, and when the first frame after those is due (INT64_MAX when E is finished or they are
+ * its last). E is not moved. frames and next_due_ms may each be NULL. CTS_E_INVALID for a null entry or schedule,
+ * max_frames == 0, S.frames_per_second == 0, or now_ms or S.base_time_ms outside [0, 2^62). Host only. */
+int cts_ms_server_frames_due(const cts_ms_server_state* state, const cts_ms_server_schedule* schedule, int64_t now_ms,
+                             uint32_t max_frames, uint32_t* frames, int64_t* next_due_ms);
+
+/* One timed tick: cts_media_stream_servers_send with every listed connection's frames released by its schedule entry
+ * at now_ms, up to max_frames of them (a connection that has fallen behind catches up in one tick). For c =
+ * dev_conn_ids[i] with E = dev_servers[c], S = dev_schedule[c], F, M and k as above, and
+ *   due(f) = S.base_time_ms + f x 1000 / S.frames_per_second     (the integer division of the product, the
+ *                                                                 reference's expression)
+ * frame f is released at now_ms when due(f) - now_ms < 2. The frames released are E.current_frame .. last, where with
+ * d = now_ms + 1 - S.base_time_ms
+ *   d < 0                                  none
+ *   d >= E.final_frame x 1000 / fps        last = E.final_frame
+ *   otherwise                              last = ((d + 1) x fps - 1) / 1000    (here (d + 1) x fps <= final_frame x
+ *                                          1000 + fps < 2^43: nothing overflows)
+ * m = max(0, last - E.current_frame + 1) of them, and the connection asks for wf = min(m, max_frames) frames.
+ *   code 4 or 2 (the plain tick's, decided first)   nothing sent, E untouched, S not read
+ *   wf == 0                                nothing sent, E untouched (code 5)
+ *   otherwise it wants w = min(wf x k, UINT32_MAX) consecutive slots, handed out by the exclusive prefix sum (64-bit) p
+ *   over the listed order, and takes t = min(wf, (capacity - min(p, capacity)) / k) whole frames:
+ *   t == 0                                 nothing sent, E untouched (code 3)
+ *   otherwise                              with `before` = E.current_frame, datagram q % k of frame before + q / k goes
+ *                                          to slot first_slot + p + q for q in [0, t x k): header, payload, descriptor
+ *                                          and length byte for byte what the plain tick writes for that frame. Then
+ *                                          E.bits_sent += 8 t F, E.datagrams_sent += t k, E.current_frame += t, and
+ *                                          E.finished = 1 once current_frame > final_frame (code 1, else 0)
+ * The written slots are first_slot .. first_slot + tick.datagrams with no gap: a connection cut by the capacity (t <
+ * wf) has pushed every later prefix past the capacity, so every running connection with a frame out that is listed
+ * after it has code 3. The tick block: the plain fields as for the plain tick (bytes = the sum of t F), frames = the
+ * sum of t, connections_waiting and next_due_ms as above. dev_udp_counters takes bits_received + 8 t F and datagrams +
+ * t k per connection.
+ * With max_frames == 1 and a frame of every listed running connection out, the entries, the ring, the descriptors,
+ * the lengths, the codes, the UDP block and the first 32 bytes of the tick block are exactly what
+ * cts_media_stream_servers_send leaves.
+ *
+ * Arguments: cts_media_stream_servers_send's, and dev_schedule non-null when n_conns != 0 and 8-byte aligned, n_conns
+ * entries; max_frames >= 1; now_ms >= 0; dev_tick (may be NULL) a cts_ms_server_timed_tick; scratch_bytes >=
+ * cts_media_stream_servers_timed_scratch_bytes(n). The caller's duties: now_ms is below 2^62 and does not decrease
+ * from tick to tick of a table, and a schedule entry comes from cts_ms_server_schedule_init (base_time_ms in [0,
+ * 2^62), frames_per_second != 0). Outside them the frame counts and the tick's tail are unspecified, but no write
+ * leaves the entries, the capacity's slots or the output arrays. */
+int cts_media_stream_servers_send_at(cts_engine* engine, void* dev_arena, uint64_t arena_bytes, uint32_t stride,
+                                     uint64_t first_slot, uint32_t capacity, const uint32_t* dev_conn_ids, uint32_t n,
+                                     cts_ms_server_state* dev_servers, const cts_ms_server_schedule* dev_schedule,
+                                     uint32_t n_conns, uint32_t max_frames, int64_t now_ms, int64_t qpc, int64_t qpf,
+                                     cts_buf_desc* dev_descs, uint32_t* dev_lengths, uint32_t* dev_codes,
+                                     cts_ms_server_timed_tick* dev_tick, void* dev_udp_counters, void* dev_scratch,
+                                     size_t scratch_bytes, void* stream);
 
 #ifdef __cplusplus
 } /* extern "C" */
